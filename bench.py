@@ -1,7 +1,7 @@
 """Headline benchmark: ssz.merkleHash of 2^28 x 32-B synthetic items (8 GiB,
 BASELINE.json configs[3]) on N MI355X, subtree-sharded.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 28] [--item-len 32]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 28] [--item-len 32] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
   python bench.py --gpus N --single-process      (one process, N devices: the cgo caller's form)
 
@@ -25,13 +25,25 @@ stay resident in HBM.  Total work is fixed as N grows ("strong" scaling);
 value = 2^log2n leaves x K / max-over-ranks wall time.  Rank 0 prints one
 JSON line; progress goes to stderr.
 
-N = 1: after the timed region, the CPU baseline (the oracle's C port with the
+A plain run (no --full) sets up, warms up, times the K steps and prints the
+line: the headline figures, the leaf-kernel roofline recorded inside the
+timed steps, and the root against its golden.  Everything that takes a run of
+its own waits for --full:
+
+--full, N = 1: after the timed region, the latency of one tree alone
+(`single_tree_ms`), the CPU baseline (the oracle's C port with the
 unrolled permutation, oracle/keccak_fast.c) and every other BASELINE config
 (C2, C3, C5, C1: tools/bench_configs.py, device-resident, 200 timed steps
 each, roots checked against tests/golden/full_size_roots.json) go into the
-same line (`side_configs`).  N > 1: rank 0 also times the whole tree on its
-GPU alone after the timed region (`single_gpu_ms`), and the line carries
-`parallel_efficiency`, every rank's leaf fraction and the aggregate fraction.
+same line (`side_configs`).  --full, N > 1: rank 0 also times the whole tree
+on its GPU alone after the timed region (`single_gpu_ms`), and the line
+carries `parallel_efficiency` beside every rank's leaf fraction and the
+aggregate fraction (both from the timed steps, so always there).
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned
+to its caller (the 32-B root) is written as DIR/root.npy, float32[32], one
+value per byte.  The inputs are seeded, so two builds given the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -231,6 +243,17 @@ def golden_root(log2n: int, item_len: int):
     return g["root"] if (g["n"], g["item_len"], g["seed"]) == (1 << log2n, item_len, SEED) else None
 
 
+def dump_outputs(path, root: bytes) -> None:
+    """--dump-outputs: the root the last timed step returned, as
+    path/root.npy (float32[32], one value per byte).  No-op without a path."""
+    if not path:
+        return
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "root.npy"), np.frombuffer(root, dtype=np.uint8).astype(np.float32))
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -261,14 +284,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--log2n", type=int, default=28)
     ap.add_argument("--item-len", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything that takes a run of its own after the timed steps: N = 1 the "
+                         "one-tree latency, the CPU baselines and the C2/C3/C5/C1 side configs; N > 1 rank 0's "
+                         "single-GPU run (parallel_efficiency).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the 32-B root, one "
+                         "float32 per byte) as DIR/root.npy")
     ap.add_argument("--cpu-sample-log2n", type=int, default=27)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-side-configs", action="store_true",
-                    help="N = 1: skip the C2/C3/C5/C1 side configs after the C4 line's own measurements")
+                    help="--full, N = 1: skip the C2/C3/C5/C1 side configs after the C4 line's own measurements")
     ap.add_argument("--side-steps", type=int, default=200)
     ap.add_argument("--side-warmup", type=int, default=40)
     ap.add_argument("--no-single-gpu", action="store_true",
-                    help="N > 1: skip rank 0's single-GPU run of the whole tree (parallel_efficiency)")
+                    help="--full, N > 1: skip rank 0's single-GPU run of the whole tree (parallel_efficiency)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend (nccl = RCCL over xGMI; gloo only to rehearse N ranks on one GPU)")
     ap.add_argument("--share-device", action="store_true",
@@ -294,6 +324,8 @@ def main():
         if "WORLD_SIZE" not in os.environ:
             return launch_ranks(args.gpus, sys.argv[1:])
     elif args.config != "c4":
+        if args.dump_outputs:
+            ap.error("--dump-outputs: only the headline (--config c4) and the N-rank c5 runs write their root")
         from tools.bench_configs import run_config
 
         return run_config(args)
@@ -495,6 +527,7 @@ def run_ranks(args, world: int, rank: int, local: int) -> int:
     leaf_ms, leaf_launches, leaf_perms, leaf_hashes = D.prof_read()
     if rank == 0 and r is not None:
         root_hex = bytes(r.cpu().numpy()).hex()
+        dump_outputs(args.dump_outputs, bytes.fromhex(root_hex))
         want = golden_root(args.log2n, item_len)
         if want is not None and root_hex != want:
             log(f"ERROR: root {root_hex} != golden {want}")
@@ -503,10 +536,10 @@ def run_ranks(args, world: int, rank: int, local: int) -> int:
     if timer is not None:
         timer.stop()  # no marks after the timed region
     phases = timer.record(world, dev if args.backend == "nccl" else None) if timer is not None else None
-    # N = 1: the latency of one complete Merkleization (one stream, not
-    # pipelined), hipEvents over >= 20 runs, after the timed region
+    # --full, N = 1: the latency of one complete Merkleization (one stream,
+    # not pipelined), hipEvents over >= 20 runs, after the timed region
     single_tree_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         runs = max(20, args.steps)
         step_one_stream()
@@ -533,11 +566,11 @@ def run_ranks(args, world: int, rank: int, local: int) -> int:
         per_rank_leaf_frac = [round(r[2] / (r[1] / 1e3) / PEAK_INT_OPS, 4) if r[1] > 0 else None for r in rows]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     t_max = t.item()
-    # N > 1: the same whole tree on rank 0's GPU alone (one stream, the
-    # N = 1 bench's step, same steps/warmup), after the timed region, so the
-    # line carries its own strong-scaling efficiency t_1 / (N t_N)
+    # --full, N > 1: the same whole tree on rank 0's GPU alone (one stream,
+    # the N = 1 bench's step, same steps/warmup), after the timed region, so
+    # the line carries its own strong-scaling efficiency t_1 / (N t_N)
     single_gpu_ms = None
-    if world > 1 and rank == 0 and not args.no_single_gpu:
+    if world > 1 and rank == 0 and args.full and not args.no_single_gpu:
         single_gpu_ms = single_gpu_step_ms(args, dev, n, item_len)
 
     if rank == 0:
@@ -615,13 +648,13 @@ def run_ranks(args, world: int, rank: int, local: int) -> int:
                 "step_frac_aggregate": tree_ops / (step_s * world * PEAK_INT_OPS),
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("timing CPU baseline ...")
             out["cpu_baseline"] = cpu_baseline(item_len, args.cpu_sample_log2n)
             # also the restatement on the host's share of cores (16 on the GPU box)
             nt = min(16, len(os.sched_getaffinity(0)))
             out["cpu_baseline_threads"] = cpu_baseline(item_len, args.cpu_sample_log2n, threads=nt)
-        if world == 1 and not args.no_side_configs:
+        if world == 1 and args.full and not args.no_side_configs:
             # every other BASELINE config, device-resident, >= 100 steps each,
             # roots against tests/golden/full_size_roots.json (tools/bench_configs.py)
             from tools.bench_configs import side_configs
@@ -743,6 +776,7 @@ def run_c5_ranks(args, world: int, rank: int, local: int) -> int:
     status = 0
     if rank == 0:
         got = bytes(r.cpu().numpy()).hex()
+        dump_outputs(args.dump_outputs, bytes.fromhex(got))
         try:
             with open(os.path.join(ROOT, "tests", "golden", "full_size_roots.json")) as f:
                 want = json.load(f)["c5"]["root"]
@@ -810,6 +844,7 @@ def run_single_process(args) -> int:
     sync_all()
     elapsed = time.perf_counter() - t0
     root_hex = bytes(out.cpu().numpy()).hex()
+    dump_outputs(args.dump_outputs, bytes.fromhex(root_hex))
     want = golden_root(args.log2n, item_len)
     res = {"metric": "tree-hash leaves/sec @2^28 chunks (ssz.merkleHash, 32-B leaves)",
            "value": n * args.steps / elapsed, "unit": "leaves/s", "n_gpus": ndev, "steps": args.steps,

@@ -1,5 +1,6 @@
 """Host-side pieces of bench.py that need no GPU: the sysfs clock parser
-the live clock sample relies on, and the golden-root lookup."""
+the live clock sample relies on, the golden-root lookup and the
+--dump-outputs writer."""
 import os
 import sys
 
@@ -54,3 +55,14 @@ def test_tree_work_counts():
     for s in (1, 3, 8, 32, 48, 128, 200):
         for n in list(range(0, 70)) + [255, 256, 257, 1000, 4099]:
             assert bench.tree_work(n, s) == walk(n, s), (n, s)
+
+
+def test_dump_outputs_writes_the_root_as_float32(tmp_path):
+    import numpy as np
+
+    root = bytes(range(224, 256))
+    bench.dump_outputs(None, root)  # no --dump-outputs: nothing written
+    bench.dump_outputs(str(tmp_path / "out"), root)
+    assert os.listdir(tmp_path / "out") == ["root.npy"]
+    a = np.load(tmp_path / "out" / "root.npy")
+    assert a.dtype == np.float32 and a.tolist() == list(range(224, 256))

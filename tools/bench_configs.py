@@ -1,7 +1,7 @@
 """The other BASELINE.json configs, single GPU: each ``measure_cX`` builds its
 device-resident inputs, checks the root against tests/golden/
 full_size_roots.json, times >= 100 steps (wall clock bracketed by
-torch.cuda.synchronize()) and returns one record.  ``bench.py`` (the
+torch.cuda.synchronize()) and returns one record.  ``bench.py --full`` (the
 driver's C4 line) runs every one of them after its own timed region and
 puts the compact records in ``side_configs``; ``bench.py --config cX`` prints
 one config's full line (``run_config``), with its CPU baseline.

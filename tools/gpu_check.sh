@@ -18,7 +18,7 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
       tail -5 $OUT/smoke.log; echo "smoke rc=$rc"; fatal $rc && exit $rc; [ $rc -ne 0 ] && exit $rc ;;
     bench)
-      timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+      timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; rc=$?
       cat $OUT/bench.json; tail -5 $OUT/bench.err; echo "bench rc=$rc"; fatal $rc && exit $rc; [ $rc -ne 0 ] && exit $rc ;;
     multirank)
       # the N-rank path (sharding, all-gather, rank-0 finish on a side stream)

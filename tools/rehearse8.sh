@@ -6,7 +6,7 @@ set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 8 --backend gloo --share-device --log2n 28 --steps 2 --warmup 1 \
+  --master-port 29517 bench.py --gpus 8 --backend gloo --share-device --log2n 28 --steps 2 --warmup 1 --full \
   --no-cpu-baseline > gpurun_out/rehearse8.json 2> gpurun_out/rehearse8.err || { tail -20 gpurun_out/rehearse8.err; exit 1; }
 grep '^{' gpurun_out/rehearse8.json | tail -1 | python -c "
 import json, sys
