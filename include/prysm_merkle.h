@@ -211,8 +211,9 @@ int mk_dev_ssz_merkle_finish_nodes_pair(mk_call* call, const void* d_nodes, uint
  * mk_dev_ssz_merkle_finish_nodes_pair (list 0's root at [0, 32), list 1's at
  * [32, 64), the struct root Keccak(d_out[0, 64)) at [64, 96) written by
  * whichever list finishes second; both finishers are in this launch, so the
- * arrival word at [96, 100) is not used; `epoch` 1 .. 2^30 - 1 is checked
- * and otherwise unused): the State root of BASELINE config 3 from the two
+ * arrival word at [96, 100) is not used; `epoch` is range-checked, 1 .. 2^30
+ * - 1, only for symmetry with the pair finishers and otherwise unused -- the
+ * launch synchronises on an arrival counter): the State root of BASELINE config 3 from the two
  * trees' level-1 nodes in one call on one stream.  Each count is 1 .. 2^20; at most
  * 4096 such launches in flight per device (arrival counters).  Workspace from
  * mk_ssz_merkle_top_fused_workspace_bytes(count0, count1), 16-B aligned.

@@ -237,16 +237,8 @@ __device__ __forceinline__ void hash_node_lock(uint4 l0, uint4 l1, uint4 r0, uin
     digest(s, d0, d1);
 }
 
-// Node-pass inputs (read once; MK_NODE_NT=1: non-temporal)
-#define MK_NODE_NT 0
-__device__ __forceinline__ uint4 ld_node(const uint4* p) {
-    if constexpr (MK_NODE_NT) {
-        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-        return make_uint4(v.x, v.y, v.z, v.w);
-    } else {
-        return ld_stream(p);
-    }
-}
+// Node-pass inputs (read once; a non-temporal load was tried and not kept)
+__device__ __forceinline__ uint4 ld_node(const uint4* p) { return ld_stream(p); }
 
 // ----------------------------------------------------------------------------
 // First-level node j of a reduce pass.
@@ -465,14 +457,13 @@ k_reduce(ReduceArgs a) {
 // instruction, each line once), and the LDS image is that flat order: lane m
 // reads its unit u at row 9 m + u (or 7 m + u - 9) -- an odd stride, so the
 // 16-B reads of any 16 consecutive lanes hit distinct bank quads.
-// MK_LOCK_NT=1 (default): the window's line 0 (units 0..7) and block 2
+// The window's line 0 (units 0..7) and block 2
 // (units 9..15, their last use) are fetched non-temporally, so they do not
 // push line 1 out of L2 between block 1's unit 8 and block 2.  Phase A is
 // then 9 instructions of line-0 units in a stride-9 image (the 9th position
 // repeats unit 7) plus one of unit 8 into rows 576..639 (160 KB of LDS).
 // One process, 2^28 (profiles/r03q): fetch 12.14 -> 8.89 GB per leaf pass
 // (1.41x -> 1.03x the algorithmic 8.59 GB), leaf pass 8.138 -> 8.071 ms.
-#define MK_LOCK_NT 1
 // The DMA of each phase in three parts spread over a permutation instead of
 // one burst (the C5 front's finding): phase B (the window's
 // second block) 3 + 2 + 2 instructions before round 0 and after rounds B1,
@@ -480,16 +471,14 @@ k_reduce(ReduceArgs a) {
 // 3 + 3 (+1) after rounds A1, A2 and MK_LOCK_DMA_ROUND of the second.  One
 // process A/B (profiles/r05/leaf_dma_split/, 7-9 interleaved rounds, two
 // boxes): 2^28 tree -0.6..-0.8 % (leaf pass 7.943 -> 7.885 ms at 2/8/14),
-// 2^25 -2.6 %.  0: one burst each (round 4's form).
-#define MK_LOCK_DMA_SPLIT 1
+// 2^25 -2.6 % against one burst each (round 4's form).
 #define MK_LOCK_SPLIT_B1 4
 #define MK_LOCK_SPLIT_B2 8
 #define MK_LOCK_SPLIT_A1 2
 #define MK_LOCK_SPLIT_A2 8
-constexpr int kLockAux = MK_LOCK_NT ? 2 : 0;  // global_load_lds aux: nt
-// the side configs' locked kernels (C2 messages, C3 records): inputs read once
-#define MK_SIDE_NT 0
-constexpr int kSideAux = MK_SIDE_NT ? 2 : 0;
+constexpr int kLockAux = 2;  // global_load_lds aux: nt
+// the side configs' locked kernels (C2 messages, C3 records): inputs read once, default policy (nt not kept)
+constexpr int kSideAux = 0;
 template <int NU, int U0, int AUX = 0, int I0 = 0, int I1 = NU>
 __device__ __forceinline__ void lock_dma_c(uint4* Bw, const uint4* __restrict__ Rj, uint32_t lane) {
     // launder the lane index so the per-lane offsets are recomputed here (a
@@ -508,21 +497,17 @@ __device__ __forceinline__ void lock_dma_c(uint4* Bw, const uint4* __restrict__ 
 // the 9 (+ the unit-8 copy with the last part)
 template <int I0 = 0, int I1 = 9>
 __device__ __forceinline__ void lock_dma_a(uint4* Bw, const uint4* __restrict__ Rj, uint32_t lane) {
-    if constexpr (!MK_LOCK_NT) {
-        lock_dma_c<9, 0, 0, I0, I1>(Bw, Rj, lane);
-    } else {
-        asm volatile("" : "+v"(lane));
+    asm volatile("" : "+v"(lane));
 #pragma unroll
-        for (int i = I0; i < I1; ++i) {
-            const uint32_t U = 64u * i + lane;
-            const uint32_t m = U / 9, u = U - m * 9;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + m * 64 + (u < 8 ? u : 7)),
-                                             (__attribute__((address_space(3))) void*)(Bw + 64 * i), 16, 0, kLockAux);
-        }
-        if constexpr (I1 == 9)
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + lane * 64 + 8),
-                                             (__attribute__((address_space(3))) void*)(Bw + 576), 16, 0, 0);
+    for (int i = I0; i < I1; ++i) {
+        const uint32_t U = 64u * i + lane;
+        const uint32_t m = U / 9, u = U - m * 9;
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + m * 64 + (u < 8 ? u : 7)),
+                                         (__attribute__((address_space(3))) void*)(Bw + 64 * i), 16, 0, kLockAux);
     }
+    if constexpr (I1 == 9)
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + lane * 64 + 8),
+                                         (__attribute__((address_space(3))) void*)(Bw + 576), 16, 0, 0);
 }
 
 // `after_wait` runs right after phase A's wait: the previous group's output
@@ -543,21 +528,16 @@ __device__ __forceinline__ void hash_window_sc(uint4* Bw, uint32_t lane, const u
         s.lo[2 * k + 1] = v.z;
         s.hi[2 * k + 1] = v.w;
     }
-    const uint4 v8 = Bw[MK_LOCK_NT ? 576 + lane : 9 * lane + 8];
+    const uint4 v8 = Bw[576 + lane];
     s.lo[16] = v8.x;
     s.hi[16] = v8.y;
 #pragma unroll
     for (int k = 17; k < 25; ++k) s.lo[k] = s.hi[k] = 0;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // rows read: phase B may overwrite them
-    if constexpr (MK_LOCK_DMA_SPLIT) {  // phase B in three parts over the first permutation
-        lock_dma_c<7, 9, kLockAux, 0, 3>(Bw, Rj, lane);
-        keccak_f_lock_mid2<MK_LOCK_SPLIT_B1, MK_LOCK_SPLIT_B2>(
-            s, [&] { lock_dma_c<7, 9, kLockAux, 3, 5>(Bw, Rj, lane); },
-            [&] { lock_dma_c<7, 9, kLockAux, 5, 7>(Bw, Rj, lane); });
-    } else {
-        lock_dma_c<7, 9, kLockAux>(Bw, Rj, lane);
-        keccak_f_lock(s);
-    }
+    lock_dma_c<7, 9, kLockAux, 0, 3>(Bw, Rj, lane);  // phase B in three parts over the first permutation
+    keccak_f_lock_mid2<MK_LOCK_SPLIT_B1, MK_LOCK_SPLIT_B2>(
+        s, [&] { lock_dma_c<7, 9, kLockAux, 3, 5>(Bw, Rj, lane); },
+        [&] { lock_dma_c<7, 9, kLockAux, 5, 7>(Bw, Rj, lane); });
     s.lo[0] ^= v8.z;
     s.hi[0] ^= v8.w;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // phase B has landed
@@ -575,16 +555,10 @@ __device__ __forceinline__ void hash_window_sc(uint4* Bw, uint32_t lane, const u
     // the next window's block 1 goes out MK_LOCK_DMA_ROUND rounds into this
     // permutation: late enough that little of the data streamed in between
     // evicts the line block 2 shares with it, early enough to land in time
-    if constexpr (MK_LOCK_DMA_SPLIT) {  // phase A of the next window in three parts
-        keccak_f_digest_lock_mid3<MK_LOCK_SPLIT_A1, MK_LOCK_SPLIT_A2, MK_LOCK_DMA_ROUND>(
-            s, [&] { if (Rnext) lock_dma_a<0, 3>(Bw, Rnext, lane); },
-            [&] { if (Rnext) lock_dma_a<3, 6>(Bw, Rnext, lane); },
-            [&] { if (Rnext) lock_dma_a<6, 9>(Bw, Rnext, lane); });
-    } else {
-        keccak_f_digest_lock<MK_LOCK_DMA_ROUND>(s, [&] {
-            if (Rnext) lock_dma_a(Bw, Rnext, lane);
-        });
-    }
+    keccak_f_digest_lock_mid3<MK_LOCK_SPLIT_A1, MK_LOCK_SPLIT_A2, MK_LOCK_DMA_ROUND>(  // in three parts
+        s, [&] { if (Rnext) lock_dma_a<0, 3>(Bw, Rnext, lane); },
+        [&] { if (Rnext) lock_dma_a<3, 6>(Bw, Rnext, lane); },
+        [&] { if (Rnext) lock_dma_a<6, 9>(Bw, Rnext, lane); });
     digest(s, d0, d1);
 }
 
@@ -597,7 +571,7 @@ __global__ __launch_bounds__(kLockThreads, 1) void k_leaf_lock_sc(ReduceArgs a, 
 #if MK_TOP_STAMPS
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_leaf_stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
-    __shared__ uint4 buf[kLockThreads / 64][(MK_LOCK_NT ? 10 : 9) * 64];
+    __shared__ uint4 buf[kLockThreads / 64][10 * 64];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4* Bw = buf[wave];
     const uint4* items = reinterpret_cast<const uint4*>(a.items);
@@ -864,7 +838,7 @@ __global__ __launch_bounds__(kReduceThreads, FAST ? MK_ELEM_WAVES : 1) void k_re
 
 template __global__ void k_reduce_elem<true>(ReduceArgs);
 
-// Phase-locked element windows (MK_ELEM_LOCK; C4 secondary, TreeHash of
+// Phase-locked element windows (C4 secondary, TreeHash of
 // [][32]byte): lane m of wave w hashes window g * 1024 + 64 w + m of group g
 // -- its 8 element digests K(le32(32) || e) (1 permutation each) and the
 // window K(d0 || .. || d7) (2) -- with phase-locked permutations and writes
@@ -1303,7 +1277,7 @@ __global__ __launch_bounds__(NT) void k_wave3(ReduceArgs a) {
     int done = 0;
     while (left > 0 && (c > 1 || a.pad_at_one)) {
         const uint64_t mn = (m + 1) / 2;
-        if (MK_WAVE3_SPREAD && mn <= NT / 64) break;  // one parent per wave from here
+        if (mn <= NT / 64) break;  // one parent per wave from here
         const bool act = k < mn;
         uint32_t l[4], r[4] = {0, 0, 0, 0};
         bool padded = false;
@@ -1329,29 +1303,12 @@ __global__ __launch_bounds__(NT) void k_wave3(ReduceArgs a) {
         --left;
         ++done;
     }
-    if (MK_WAVE3_SPREAD) wave3_spread_levels<NT>(lds, c, m, left, done, a.pad_at_one);
+    wave3_spread_levels<NT>(lds, c, m, left, done, a.pad_at_one);
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
-    if (MK_WAVE3_SPREAD && a.finalize) {
+    if (a.finalize) {
         if (tid < 64)
             wave3_spread_final(lds, a.n_items, out, reinterpret_cast<uint32_t*>(a.pair_block), a.pair_slot,
                                a.pair_epoch);
-    } else if (a.finalize) {
-        if (k == 0) {  // K(root || le64(n) || 0^24) on lanes 0/1
-            ilv::Half s;
-            ilv::zero(s);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) s.v[w] = lds[2 * w + p];
-            s.v[4] = ilv::to_ilv((uint32_t)a.n_items, (uint32_t)(a.n_items >> 32), p);
-            if (p == 0)
-                s.v[8] ^= 1u;
-            else
-                s.v[16] ^= 0x80000000u;
-            ilv::keccak_f(s, p);
-            uint32_t d[4];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) d[w] = s.v[w];
-            store_node3(out, 0, false, p, d);
-        }
     } else if (k < m) {
         const uint64_t lo_out = lo1 >> done;
         uint32_t d[4];
@@ -1377,9 +1334,8 @@ template __global__ void k_wave3<1024, true>(ReduceArgs);
 // where the locked waves otherwise take most of the issue slots and the top's
 // dependent chain, not the front, sets the step.  One
 // process A/B (profiles/r05/c5_front_ab/ab_knobs.txt): the pipelined stream
-// 0.4386 -> 0.4231 ms/step at priority 1 (0.4239 at 3); 0 = the default
-// wave priority.
-#define MK_TRIE_TOP_PRIO 1
+// 0.4386 -> 0.4231 ms/step at priority 1 (0.4239 at 3, 0.4386 at the default 0).
+constexpr int kTrieTopPrio = 1;
 // Narrow top of the deposit trie, bit-interleaved lane pairs (mk::ilv): the
 // workgroup owns NT input nodes of level d (NT/2 lane pairs) and writes
 // `levels` levels to the (plain) level array; once the count is 1 it goes on
@@ -1389,7 +1345,7 @@ template __global__ void k_wave3<1024, true>(ReduceArgs);
 template <uint32_t NT>
 __global__ __launch_bounds__(NT) void k_trie_top3(const uint32_t* __restrict__ in, uint64_t cin,
                                                   uint32_t* __restrict__ lv_out, uint32_t levels, uint64_t capn) {
-    if constexpr (MK_TRIE_TOP_PRIO > 0) __builtin_amdgcn_s_setprio(MK_TRIE_TOP_PRIO);
+    __builtin_amdgcn_s_setprio(kTrieTopPrio);
     constexpr uint32_t kPairs = NT / 2;
     __shared__ uint32_t lds[8 * kPairs];
     const uint32_t tid = threadIdx.x, k = tid >> 1, p = tid & 1u;
@@ -1466,16 +1422,10 @@ __global__ __launch_bounds__(256, MK_K64_WAVES) void k_keccak64(const uint4* __r
     out[2 * i + 1] = d1;
 }
 
-// digest outputs nobody in this kernel reads again: non-temporal with MK_SIDE_NT
-__device__ __forceinline__ void st_out(uint4* p, uint4 v) {
-    if constexpr (MK_SIDE_NT) {
-        __builtin_nontemporal_store(*reinterpret_cast<const u32x4_t*>(&v), reinterpret_cast<u32x4_t*>(p));
-    } else {
-        *p = v;
-    }
-}
+// digest outputs nobody in this kernel reads again (a non-temporal store was tried and not kept)
+__device__ __forceinline__ void st_out(uint4* p, uint4 v) { *p = v; }
 
-// Phase-locked 64-B messages (MK_K64_LOCK; C2 and 64-B node pairs) for n =
+// Phase-locked 64-B messages (C2 and 64-B node pairs) for n =
 // 1024 * ngroups messages, the rest by k_keccak64.  1024-thread workgroups,
 // one per CU, persistent; lane m of wave w hashes message g * 1024 + 64 w + m
 // (one phase-locked permutation).  The wave's 64 messages (4 KB, contiguous)
@@ -1945,7 +1895,7 @@ __global__ __launch_bounds__(kStructThreads, MK_STRUCT_REG_WAVES) void k_struct_
 }
 template __global__ void k_struct_reg<3, 6>(const uint8_t*, uint64_t, StructSpec, uint32_t, uint4*);
 
-// Phase-locked struct roots (MK_STRUCT_LOCK) for the validator layout of
+// Phase-locked struct roots for the validator layout of
 // SURVEY §8d (ValidatorRecord: Pubkey 48 B @0, WithdrawalCredentialsHash32
 // 32 B @48, RandaoCommitmentHash32 32 B @80, six uint64 @112..152; 160-B
 // records, 16-B aligned; the host checks the StructSpec against
@@ -2448,7 +2398,7 @@ __global__ __launch_bounds__(kRecThreads, MK_REC_WAVES) void k_keccak_rec(const 
 }
 template __global__ void k_keccak_rec<35>(const uint2*, uint64_t, uint4*);
 
-// Phase-locked deposit-trie front (MK_TRIE_LOCK): the leaf hashes of 280-B
+// Phase-locked deposit-trie front: the leaf hashes of 280-B
 // deposits (deposit_trie.go:32, Hash(depositData)) AND the trie levels above
 // them up to the node over DPT leaves (deposit_trie.go:33-38), in one launch.
 // Every thread owns DPT consecutive deposits: 3 permutations each (2 full
@@ -2469,7 +2419,7 @@ template __global__ void k_keccak_rec<35>(const uint2*, uint64_t, uint4*);
 // Whole groups only (the host runs the rest with k_keccak_rec + k_trie_level).
 // global_load_lds policy of the deposit DMA: 0 (nt = 2: +0.7 % on the
 // pipelined stream, profiles/r05/c5_front_ab/)
-#define MK_TRIE_LOCK_AUX 0
+constexpr int kTrieLockAux = 0;
 // The next block's 9-unit DMA goes out in parts spread over the current
 // block's permutation: units 0-2, 3-5, 6-8 after rounds MK_TRIE_DMA_SPLIT,
 // MK_TRIE_DMA_SPLIT3 and MK_TRIE_DMA_ROUND (SPLIT3 = 0: units 0-4 / 5-8
@@ -2524,7 +2474,7 @@ __global__ __launch_bounds__(NT, 1) void k_trie_rec_lock(const uint2* __restrict
             const uint32_t start = (DPT * m + i) * (8 * NW) + 136 * b;
             __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(region + (start & ~15u) + 16 * u),
                                              (__attribute__((address_space(3))) void*)(Bw + 64 * k), 16, 0,
-                                             MK_TRIE_LOCK_AUX);
+                                             kTrieLockAux);
         }
     };
     // a node is stored after the next slot's first wait, so no wait covers a
@@ -2745,7 +2695,7 @@ __global__ __launch_bounds__(NT, 1) void k_trie_rec_lock_sm(const uint2* __restr
             const uint32_t start = m * (8 * NW) + 136 * b;
             __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(region + (start & ~15u) + 16 * u),
                                              (__attribute__((address_space(3))) void*)(Bw + 64 * k), 16, 0,
-                                             MK_TRIE_LOCK_AUX);
+                                             kTrieLockAux);
         }
     };
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;  // a node stored after the next wait
@@ -3088,7 +3038,7 @@ template <uint32_t NW>
 __global__ __launch_bounds__(64 * NW) void k_trie_spread(uint32_t* __restrict__ levels, uint64_t cap, uint32_t d0,
                                                          uint64_t lo, uint64_t c, uint32_t d_end, uint32_t depth,
                                                          uint32_t* __restrict__ root_out, SpreadLeaves lv) {
-    if constexpr (MK_TRIE_TOP_PRIO > 0) __builtin_amdgcn_s_setprio(MK_TRIE_TOP_PRIO);
+    __builtin_amdgcn_s_setprio(kTrieTopPrio);
     __shared__ uint2 lds[2][4 * NW];
     const uint32_t w = threadIdx.x >> 6, L = threadIdx.x & 63u;
     const spread::LaneLH cst = spread::lane_consts_lh(L);
@@ -3166,7 +3116,7 @@ template __global__ void k_trie_spread<16>(uint32_t*, uint64_t, uint32_t, uint64
 __global__ __launch_bounds__(64) void k_trie_append1(uint32_t* __restrict__ levels, uint64_t cap, uint64_t count,
                                                      uint32_t depth, uint32_t* __restrict__ root_out,
                                                      SpreadLeaves lv) {
-    if constexpr (MK_TRIE_TOP_PRIO > 0) __builtin_amdgcn_s_setprio(MK_TRIE_TOP_PRIO);
+    __builtin_amdgcn_s_setprio(kTrieTopPrio);
     __shared__ uint2 sib[64][4];
     const uint32_t L = threadIdx.x;
     const spread::LaneLH cst = spread::lane_consts_lh(L);
@@ -3242,7 +3192,7 @@ __global__ __launch_bounds__(64) void k_trie_append1(uint32_t* __restrict__ leve
 // narrow one-workgroup launch waiting for the wide one.
 
 // Arrival counters of the fused tops, one per launch in flight (the host
-// hands out slots round-robin, capi.cpp next_arrive_slot); zero at module
+// hands out slots round-robin, merkle_api.cpp next_arrive_slots); zero at module
 // load, and the last arriver of a launch resets its slot, so at most
 // kArriveSlots fused launches may be in flight on one device.
 __device__ uint32_t g_arrive[kArriveSlots];
@@ -3474,7 +3424,8 @@ __device__ __forceinline__ bool wg_arrive_last(uint32_t slot, uint32_t total, ui
 // them), the last workgroup to arrive the rest, including the zero-sibling
 // levels (deposit_trie.go:33-38) and the root.  grid = ceil(c0 / NT) <= NT;
 // a grid of more than kTopGroup workgroups also uses the arrival slots after
-// `slot`, one per group of each stage (kTopGroupSlots in all at most).
+// `slot`, one per group of each stage: the top_arrive_slots(grid) slots the
+// host reserved for this launch (never more than kTopGroupSlots).
 template <uint32_t NT>
 __global__ __launch_bounds__(NT) void k_trie_top_fused(uint32_t* __restrict__ levels, uint64_t cap, uint64_t c0,
                                                        uint32_t d0, uint32_t depth, uint32_t* __restrict__ root_out,

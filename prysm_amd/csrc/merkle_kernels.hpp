@@ -60,20 +60,18 @@ struct StructPrev {
 template <bool PREV>
 __global__ void k_struct_lock(const uint8_t* rec, uint64_t n, uint4* roots, uint32_t gpw, uint4* wins,
                               const uint8_t* vals, uint64_t vbytes, uint4* vwins, StructPrev prev);
-#define MK_STRUCT_LOCK 1
 template <int NB, int NRAW>
 __global__ void k_struct_split(const uint8_t* rec, uint64_t n, StructSpec sp, uint32_t vec16, uint4* roots);
 #define MK_STRUCT_SPLIT_MAX_N 32768
 constexpr uint64_t kStructSplitMaxN = MK_STRUCT_SPLIT_MAX_N;  // k_struct_split at or below (0: never)
 template <uint32_t NT, bool LEAF>
 __global__ void k_wave3(ReduceArgs a);
-#define MK_WAVE3_SPREAD 1  // k_wave3's last levels one state per wave (the pair finalize needs it)
+// k_wave3's last levels run one state per wave (the pair finalize needs that form)
 __global__ void k_final_small(const uint8_t* items, uint64_t total, uint64_t n, uint8_t* out);
 __global__ void k_keccak64(const uint4* in, uint64_t n, uint4* out);
 __global__ void k_keccak64_lock(const uint4* in, uint64_t n, uint4* out);  // any n (a partial last group)
 // phase-locked node pass: ngroups whole groups of 1024 x kNodeLockPairs complete node pairs, persistent grid
 __global__ void k_node_lock(ReduceArgs a, uint64_t ngroups);
-#define MK_K64_LOCK 1
 __global__ void k_keccak_fixed(const uint8_t* in, uint64_t n, uint32_t msg_len, uint4* out);
 __global__ void k_keccak_var(const uint8_t* in, const uint64_t* offs, uint64_t n, uint4* out);
 __global__ void k_trie_level(const uint4* in, uint64_t cin, uint4* out);
@@ -95,7 +93,6 @@ __global__ void k_trie_rec_lock(const uint2* in, uint64_t ngroups, uint4* L0, ui
                                 TriePrev prev);
 template <uint32_t NT>
 __global__ void k_trie_rec_lock_sm(const uint2* in, uint64_t ngroups, uint4* L0, uint4* L1, uint4* L2);
-#define MK_TRIE_LOCK 1
 #define MK_TRIE_LOCK_GRID 256  // persistent grid cap
 #define MK_TRIE_LOCK_MIN (1u << 18)  // deposits: at least one group per CU
 
@@ -111,7 +108,6 @@ __global__ void k_verify_branches(const uint4* leaves, const uint4* branches, co
 template <uint32_t NT>
 __global__ void k_trie_append(uint32_t* levels, uint64_t cap, uint32_t d0, uint64_t lo, uint64_t c, uint32_t d_end,
                               uint32_t depth, uint32_t* root_out);
-#define MK_TRIE_SPREAD 1
 #define MK_SPREAD_WAVES_MAX 16
 constexpr uint32_t kSpreadWavesMax = MK_SPREAD_WAVES_MAX;  // k_trie_spread: one state per wave (<= 4 per SIMD)
 template <uint32_t SPAN>
@@ -132,13 +128,14 @@ __global__ void k_trie_spread(uint32_t* levels, uint64_t cap, uint32_t d0, uint6
                               uint32_t depth, uint32_t* root_out, SpreadLeaves lv);
 // fused tree tops: arrival counter slots (one per fused launch in flight)
 constexpr uint32_t kArriveSlots = 4096;
-// k_trie_top_fused: the last of each kTopGroup workgroups reduces the group's
-// nodes before the last group finishes the top
-// nodes before the next stage / the last group finishes the top (0: the last
-// workgroup alone reduces all the grid's nodes)
+// k_trie_top_fused, k_merkle_top_fused: the last of each kTopGroup workgroups
+// to arrive reduces the group's nodes before the next stage / the last group
+// finishes the top (0: the last workgroup alone reduces all the grid's nodes)
 #define MK_TOP_GROUP_LOG2 4
 constexpr uint32_t kTopGroupLog2 = MK_TOP_GROUP_LOG2, kTopGroup = 1u << kTopGroupLog2;
-constexpr uint32_t kTopGroupSlots = kTopGroupLog2 ? 1 + 2 * 1024 / kTopGroup : 1;  // arrival slots of one launch
+// upper bound of the arrival slots one launch uses (a 1024-workgroup grid); a
+// launch reserves only top_arrive_slots(parts) of them (merkle_api.cpp)
+constexpr uint32_t kTopGroupSlots = kTopGroupLog2 ? 1 + 2 * 1024 / kTopGroup : 1;
 template <uint32_t NT>
 __global__ void k_trie_top_fused(uint32_t* levels, uint64_t cap, uint64_t c0, uint32_t d0, uint32_t depth,
                                  uint32_t* root_out, uint32_t slot);
@@ -151,7 +148,7 @@ struct MerkleTopList {
     uint32_t* out;       // the list root (32 B; with a pair: its slot of the pair block)
     uint32_t wg0, nwg;   // this list's workgroups
     uint32_t span_log2;  // level nodes per workgroup
-    uint32_t slot;       // first of its arrival counters (g_arrive; capi.cpp top_arrive_slots)
+    uint32_t slot;       // first of its arrival counters (g_arrive; merkle_api.cpp top_arrive_slots)
 };
 struct MerkleTopArgs {
     MerkleTopList l[2];

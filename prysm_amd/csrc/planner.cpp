@@ -76,7 +76,6 @@ constexpr uint64_t kLockSpans = 4;  // k_reduce spans (1024 windows) per k_leaf_
 // 2^28 (profiles/r05/node_lock/): whole tree 9.004 -> 8.871 ms (the node pass
 // 0.836 -> 0.689 ms by rocprof), 9 interleaved rounds.
 constexpr uint64_t kNodeLockGroupMul = 256;
-#define MK_NODE_LOCK 1
 
 uint32_t ilog2(uint64_t v) {
     uint32_t l = 0;
@@ -193,7 +192,7 @@ int make_plan(uint64_t n, uint32_t item_len, bool subtree, uint32_t height, bool
                           a.c1_full >= kLeafLockMinC1 && remaining > kLockLevels &&
                           a.c1_full / span >= kLockSpans;
         if (lock) lv = kLockLevels;
-        const uint64_t nodelock = (MK_NODE_LOCK && !leaf && !wave && !final_pass && ni == 2 && remaining > kNodeLockLevels &&
+        const uint64_t nodelock = (!leaf && !wave && !final_pass && ni == 2 && remaining > kNodeLockLevels &&
                                    (in_slot >= 0 || aligned16))
                                       ? (a.c1_full / span) / kNodeLockSpans / kNodeLockGroupMul * kNodeLockGroupMul
                                       : 0;

@@ -1,0 +1,165 @@
+// Internal header of libprysm_merkle.so's host side: the device context and
+// call scope (runtime.cpp) and every function that crosses translation units
+// (hash_api, merkle_api, struct_api, trie_api, multi_api, capi).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "merkle_kernels.hpp"
+#include "planner.hpp"
+#include "prysm_merkle.h"
+
+#define HIPCHK(x)                                                                            \
+    do {                                                                                     \
+        hipError_t e_ = (x);                                                                 \
+        if (e_ != hipSuccess) return mk::fail(MK_EHIP, "%s: %s", #x, hipGetErrorString(e_)); \
+    } while (0)
+
+#define TRY(x)                        \
+    do {                              \
+        int rc_ = (x);                \
+        if (rc_ != MK_OK) return rc_; \
+    } while (0)
+
+namespace mk::rt {
+
+// ---- devices (runtime.cpp) -------------------------------------------------
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+int grow(DevBuf& b, size_t bytes);
+
+// small pinned upload ring: descriptor tables for dev entry points (the
+// source must outlive the async copy; a slot is reused after its event)
+struct SmallStage {
+    std::mutex mu;
+    static constexpr int kSlots = 4;
+    void* host[kSlots] = {};
+    size_t cap[kSlots] = {};
+    hipEvent_t ev[kSlots] = {};
+    bool used[kSlots] = {};
+    int next = 0;
+};
+
+struct DevCtx {
+    std::mutex mu;  // host-buffer entry points: in/out/ws/aux and the big staging
+    hipStream_t stream = nullptr;
+    DevBuf in, out, ws, aux, dig;  // dig: element digests of the multi-shard TreeHash path
+    // side stream + events: the ragged last workgroup of a pass runs
+    // concurrently with the pass's full workgroups (fork/join on events)
+    std::mutex side_mu;
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+
+    // host-buffer uploads on `copy` overlapping compute on `stream`
+    hipStream_t copy = nullptr;
+    hipEvent_t h2d = nullptr;
+    hipEvent_t region_ev[2] = {nullptr, nullptr};  // multi: compute of a shard region done
+    bool region_used[2] = {false, false};
+    SmallStage small;
+    // mk_dev_ssz_merkle_hash_multi's own frontier blocks / workspaces: that
+    // path enqueues on the caller's streams without this device's `mu`, so it
+    // must never share in/out/ws/aux with the host-buffer entry points
+    DevBuf mout, mws, maux;
+};
+
+extern std::vector<DevCtx*> g_ctx;  // one per visible device, created by bind_dev
+extern thread_local int t_bound;    // device bound by the current call
+inline DevCtx* ctx() { return g_ctx[t_bound]; }
+
+int probe_devices();  // visible gfx950 devices
+int bind_dev(int dev);
+int bind_call();
+int bind_stream(hipStream_t st);
+int upload_small(DevCtx* c, void* d_dst, const void* src, size_t bytes, hipStream_t st);
+bool inject_ehip();
+uint64_t lock_grid_cap(hipStream_t st);
+inline int launched() {  // after a kernel launch: MK_OK, or MK_EHIP with the launch's error
+    HIPCHK(hipGetLastError());
+    return MK_OK;
+}
+
+// Per-call scope of an extern "C" entry point: installs the call context,
+// restores the thread's current device on exit.
+struct Scope {
+    mk_call* prev;
+    int saved = -1;
+    bool restore = false;
+    explicit Scope(mk_call* c, bool gpu = true) {
+        prev = mk::swap_call(c);
+        if (c) {
+            c->code = MK_OK;
+            c->err[0] = 0;
+        }
+        if (gpu && probe_devices() > 0) restore = hipGetDevice(&saved) == hipSuccess;
+    }
+    int done(int rc) {
+        if (mk::current_call()) mk::current_call()->code = rc;
+        return rc;
+    }
+    ~Scope() {
+        int cur = -1;
+        if (restore && hipGetDevice(&cur) == hipSuccess && cur != saved) (void)hipSetDevice(saved);
+        t_bound = -1;
+        mk::swap_call(prev);
+    }
+};
+
+// Prologue of a device entry point: the call scope, the stream's device, then
+// `body` (its argument checks and launches, in that order).
+template <class F>
+inline int dev_entry(mk_call* call, void* stream, const F& body) {
+    Scope S(call);
+    const int rc = bind_stream((hipStream_t)stream);
+    return S.done(rc ? rc : body());
+}
+
+// ---- measurement (runtime.cpp) -----------------------------------------------
+// One timed launch (or group of launches) of a leaf pass, mk_prof_read's input.
+struct ProfRec {
+    hipEvent_t a, b;
+    double perms, hashes;
+};
+bool prof_on();
+void prof_enable(bool on);
+int prof_begin(ProfRec& r, hipStream_t st);                               // creates the events, records r.a
+int prof_end(ProfRec& r, double perms, double hashes, hipStream_t st);  // records r.b and files the record
+int prof_read(double* leaf_ms, uint64_t* leaf_launches, double* leaf_perms, double* leaf_hashes);
+
+// ---- hashing (hash_api.cpp) ----------------------------------------------------
+int dev_hash_batch(const void* d_in, uint64_t n, uint32_t msg_len, void* d_out, hipStream_t st);
+int dev_hash_var(const void* d_in, const uint64_t* d_offs, uint64_t n, void* d_out, hipStream_t st);
+int64_t uniform_len(const uint64_t* offs, uint64_t n);  // uniform message length of offs[0..n] (relative), or -1
+
+// ---- merkleHash (merkle_api.cpp) -------------------------------------------------
+inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+int launch_plan(const Plan& p, const uint8_t* d_items, uint8_t* d_out32, uint8_t* d_ws, uint64_t ws_bytes,
+                hipStream_t st, uint8_t* pair_block = nullptr, uint32_t pair_slot = 0, uint32_t pair_epoch = 0);
+bool list_tree_ok(uint64_t n, uint32_t item_len);      // the latency form of a small list's tree applies
+uint64_t list_tree_ws(uint64_t n, uint32_t item_len);  // its workspace (0: not that form)
+int dev_merkle_hash(const void* d_items, uint64_t n, uint32_t item_len, void* d_out32, void* d_ws, uint64_t ws_bytes,
+                    hipStream_t st);
+int dev_finish(const void* d_roots, uint64_t nroots, uint64_t n_total, void* d_out32, hipStream_t st,
+               void* d_pair_block = nullptr, uint32_t pair_slot = 0, uint32_t pair_epoch = 0);
+uint64_t finish_ws_bytes(uint64_t count);
+int dev_finish_nodes(const void* d_nodes, uint64_t count, uint64_t n_total, void* d_out32, void* d_ws,
+                     uint64_t ws_bytes, hipStream_t st, void* d_pair_block = nullptr, uint32_t pair_slot = 0,
+                     uint32_t pair_epoch = 0);
+int launch_elem_digests(const void* d_elems, uint64_t n, uint32_t elem_len, void* d_dig, hipStream_t st);
+int host_tree_hash_elems_plain(const uint8_t* elems, uint64_t n, uint32_t elem_len, uint8_t* out);
+int host_merkle_hash_plain(const uint8_t* items, uint64_t n, uint32_t item_len, uint8_t* out);
+// arrival-counter slots of the fused tops (mk::g_arrive): also the trie's and the struct list's
+uint32_t next_arrive_slots(uint32_t k);
+uint32_t top_arrive_slots(uint64_t parts);
+
+// ---- multi-device (multi_api.cpp) ------------------------------------------------
+int host_merkle_multi(const uint8_t* items, uint64_t n, uint32_t item_len, int nshards, const int* devs_in,
+                      uint8_t* out, uint32_t elem_len = 0);
+
+}  // namespace mk::rt

@@ -116,7 +116,7 @@ class TriePipeline:
     (so the root's timing depends on the shape: only for callers that always
     flush() before reading roots)."""
 
-    TOP_MAX = 1 << 17  # capi.cpp kTrieTopMax: levels at or below this width run k_trie_top3
+    TOP_MAX = 1 << 17  # trie_api.cpp kTrieTopMax: levels at or below this width run k_trie_top3
     PIPE_TOP_FROM = 7  # the last level the pipelined front builds for the previous trie
 
     def __init__(self, n: int, deposit_len: int, depth: int, device, split: Optional[int] = None,

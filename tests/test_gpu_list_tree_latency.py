@@ -1,4 +1,4 @@
-"""The latency form of a small list's tree (capi.cpp dev_list_tree_32:
+"""The latency form of a small list's tree (merkle_api.cpp dev_list_tree:
 k_spread_leaf<8> + k_merkle_top_fused in spans of 16 nodes) for the TreeHash
 of a []ValidatorRecord (hash.go:118-139 -> merkleHash, hash.go:194-239),
 device records, at every boundary of the form: the first size that takes it

@@ -27,7 +27,7 @@ static void print_wgs(const std::vector<uint64_t>& st, uint32_t b0, uint32_t b1,
 }
 
 // C3's fused list top (k_merkle_top_fused): 125,000 registry + 31,250
-// balances level-1 nodes, spans 1024 / 256 (capi.cpp top_plan)
+// balances level-1 nodes, spans 1024 / 256 (merkle_api.cpp top_plan)
 static int merkle_probe(int iters) {
     const uint64_t c0 = 125000, c1 = 31250;
     uint32_t *n0, *n1, *ws, *pair;
