@@ -45,7 +45,7 @@
  *     refuse / are not meant for capture.
  *   - Thread safety: every entry point may be called concurrently from any OS
  *     thread; host-buffer entry points take a per-device lock, deposit-trie
- *     handles a per-handle lock.
+ *     and list-tree handles a per-handle lock.
  *   - Digests are 32 bytes; node arrays are n x 32 contiguous bytes.
  */
 #ifndef PRYSM_MERKLE_H
@@ -133,6 +133,69 @@ int mk_dev_ssz_tree_hash_bytes_list(mk_call* call, const void* d_elems, uint64_t
                                     void* d_out32, void* d_ws, uint64_t ws_bytes, void* stream);
 int mk_ssz_tree_hash_bytes_list(mk_call* call, const uint8_t* elems, uint64_t n, uint32_t elem_len,
                                 uint8_t out[32]);
+
+/* ---- device-resident list tree: merkleHash re-hashed from changed items --- */
+/* The tree of ssz.merkleHash over n items of item_len bytes (flat,
+ * contiguous), every level kept in HBM, so that a changed or appended item
+ * costs its chunk's ancestors (O(changed x depth) hashes) instead of the
+ * whole list.  Layout: p = 128 / item_len items per chunk (1 when item_len >=
+ * 128), nchunks = ceil(n / p), cap_chunks the same of `capacity`.  Level 0 is
+ * the caller's item buffer and is never copied.  Level d (1 <= d <= D, D the
+ * first level with ceil(cap_chunks / 2^d) == 1) starts at node
+ * sum_{1<=i<d} ceil(cap_chunks / 2^i) of the level array and holds
+ * ceil(nchunks / 2^d) nodes of 32 B: node j = Keccak(child 2j || child 2j+1),
+ * a missing right child being 0^128 (hash.go:229-236).  Every level up to the
+ * current top (the first with one node) is stored; nodes beyond those counts
+ * and levels above the top are unspecified.  root = Keccak(top || le64(n) ||
+ * 0^24); with nchunks <= 1 there are no levels and top is the raw chunk
+ * (0^128 when n == 0).  A grown tree gains levels above its old top, which
+ * stays node 0 of its level.  item_len is 1 .. 2^30.
+ * mk_ssz_list_tree_levels_bytes: bytes of the level array (0 for item_len ==
+ * 0 or cap_chunks <= 1); d_levels is 16-B aligned.
+ * Replaces: ssz.merkleHash (shared/ssz/hash.go:194-239) for a list whose tree
+ * is already built. */
+uint64_t mk_ssz_list_tree_levels_bytes(uint64_t capacity, uint32_t item_len);
+/* All levels and the root of n <= capacity items. */
+uint64_t mk_ssz_list_tree_build_workspace_bytes(uint64_t n, uint32_t item_len);
+int mk_dev_ssz_list_tree_build(mk_call* call, const void* d_items, uint64_t n, uint64_t capacity, uint32_t item_len,
+                               void* d_levels, void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream);
+/* Re-hash after a change: d_idx holds k_idx strictly ascending item indices
+ * < n_old (device memory) whose items changed; items [n_old, n_new) are
+ * appended (n_old <= n_new <= capacity).  d_values != NULL: k_idx new item
+ * values, then n_new - n_old appended ones, item_len bytes each, scattered
+ * into d_items first by the same call; NULL: the caller has already written
+ * the new bytes into d_items on this stream.  Recomputes exactly the
+ * ancestors of the changed chunks and writes the root to d_root32 (also when
+ * nothing changed).  An index >= n_old is ignored; a list that is not
+ * ascending gives an undefined root but no access outside the buffers.
+ * Workspace (8-B aligned) from mk_ssz_list_tree_update_workspace_bytes(k),
+ * k = k_idx + n_new - n_old (< 2^31): the call zeroes and owns it until it has
+ * run, so trees updated concurrently on different streams need a workspace
+ * each; too small is MK_ENOMEM.  item_len == 0, n_new < n_old and n_new >
+ * capacity are MK_EINVAL. */
+uint64_t mk_ssz_list_tree_update_workspace_bytes(uint64_t k);
+int mk_dev_ssz_list_tree_update(mk_call* call, void* d_items, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                                uint32_t item_len, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
+                                const void* d_values, void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream);
+/* Handle form for host callers: items and levels stay in HBM under a
+ * per-handle lock (the validator registry's roots, the balances).  update
+ * takes host indices in any order (list[idx[j]] = values[j] in sequence: of a
+ * repeated index the last value wins; an index >= count is MK_EINVAL and
+ * nothing changes) and uploads only the k indices and values; append past the
+ * capacity doubles it and rebuilds; a call that dirties 1/512 of the list or
+ * more rebuilds instead of climbing.  The root of a new handle is
+ * merkleHash([]). */
+typedef struct mk_list_tree mk_list_tree;
+int mk_list_tree_new(mk_call* call, uint32_t item_len, uint64_t capacity, mk_list_tree** out);
+void mk_list_tree_free(mk_list_tree* t);
+uint64_t mk_list_tree_count(const mk_list_tree* t);
+/* Replaces the whole list by n items. */
+int mk_list_tree_assign(mk_call* call, mk_list_tree* t, const uint8_t* items, uint64_t n);
+int mk_list_tree_update(mk_call* call, mk_list_tree* t, const uint64_t* idx, const uint8_t* values, uint64_t k);
+int mk_list_tree_append(mk_call* call, mk_list_tree* t, const uint8_t* items, uint64_t k);
+int mk_list_tree_root(mk_call* call, mk_list_tree* t, uint8_t root[32]);
+/* Items [first, first + cnt), cnt x item_len bytes. */
+int mk_list_tree_items(mk_call* call, mk_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
 
 /* ---- subtree sharding across GPUs ----------------------- */
 /* Split a merkleHash of n items over `nshards` devices: every shard is a

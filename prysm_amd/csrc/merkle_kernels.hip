@@ -4034,4 +4034,214 @@ __global__ __launch_bounds__(256) void k_many_final(const uint8_t* __restrict__ 
     roots[2 * i + 1] = d1;
 }
 
+// ----------------------------------------------------------------------------
+// Device-resident list tree: merkleHash (hash.go:194-239) of
+// a list whose every level stays in HBM, re-hashed from the changed items
+// only.  Level d >= 1 of the level array starts at node sum_{1<=i<d}
+// ceil(cap_chunks / 2^i); level 0 is the item buffer itself.
+//
+// Work item t < T = k_idx + (n_new - n_old) is one dirty item: idx[t] for
+// t < k_idx (ascending; an index >= n_old is read as the last old item, whose
+// ancestors are then recomputed to the values they already have), after them
+// the appended items n_old .. n_new - 1.  A lane pair (mk::ilv) serves a work
+// item.  The pair of the FIRST work item under a level-1 node hashes that node
+// from the item buffer and climbs; every node it finishes is stored, and it
+// owns the work items [o, e) under that node.  Whether the sibling changed
+// too is decided locally from the sorted list (item o - 1 for a left
+// sibling, item e for a right one):
+//   clean: the sibling (or the 0^128 pad when it does not exist) is read from
+//          the level array, which an earlier launch wrote;
+//   dirty: both children's pairs OR bit d into the arrival word of the
+//          parent's first work item; the pair that finds the bit set (the
+//          second to arrive) hashes the parent, the other one exits.
+// No pair ever waits for another, so the launch completes whatever the grid
+// size and dispatch order.  Ordering contract of the hand-off (the fence form,
+// both sides): node stores -> __threadfence() (agent release) -> acq_rel
+// agent-scope atomic OR; the second arriver: that atomic -> __threadfence()
+// (agent acquire) -> loads of the sibling (agent-scope, so neither the
+// compiler nor the CU's L1 can serve them from before the fence).
+// The arrival words (one per work item, zeroed on the stream by the same
+// call) are the caller's workspace: two trees never share one.
+namespace {
+
+__device__ __forceinline__ uint64_t lt_chunk(const ListTreeArgs& a, uint64_t t) {
+    uint64_t x;
+    if (t < a.k_idx) {
+        x = a.idx[t];
+        const uint64_t last = a.n_old ? a.n_old - 1 : 0;
+        if (x > last) x = last;
+    } else {
+        x = a.n_old + (t - a.k_idx);
+    }
+    return x / a.per;
+}
+
+// first work item in [from, T] whose level-d node is above j (T: none); a
+// gallop then a bisection, both bounded for any list contents
+__device__ __forceinline__ uint64_t lt_upper(const ListTreeArgs& a, uint64_t from, uint64_t T, uint32_t d,
+                                             uint64_t j) {
+    uint64_t lo = from, hi = T, step = 1;
+    while (lo < hi && step <= hi - lo) {
+        const uint64_t probe = lo + step - 1;
+        if ((lt_chunk(a, probe) >> d) > j) {
+            hi = probe;
+            break;
+        }
+        lo = probe + 1;
+        step <<= 1;
+    }
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((lt_chunk(a, mid) >> d) > j)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+
+// first work item in [0, upto] whose level-d node is at least j (item `upto` is one)
+__device__ __forceinline__ uint64_t lt_lower(const ListTreeArgs& a, uint64_t upto, uint32_t d, uint64_t j) {
+    uint64_t lo = 0, hi = upto, step = 1;
+    while (lo < hi && step <= hi - lo) {
+        const uint64_t probe = hi - step;
+        if ((lt_chunk(a, probe) >> d) >= j) {
+            hi = probe;
+            step <<= 1;
+        } else {
+            lo = probe + 1;
+            break;
+        }
+    }
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((lt_chunk(a, mid) >> d) >= j)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+
+// plain node j of a level -> this lane's parity words, agent-scope loads
+__device__ __forceinline__ void lt_load_node(const uint32_t* lv, uint64_t j, uint32_t p, uint32_t (&w4)[4]) {
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(lv) + 4 * j;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint64_t v = __hip_atomic_load(q + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w4[w] = ilv::to_ilv((uint32_t)v, (uint32_t)(v >> 32), p);
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_list_tree_update(ListTreeArgs a) {
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t = gid >> 1;
+    const uint32_t p = (uint32_t)(gid & 1u);
+    const uint64_t T = a.k_idx + (a.n_new - a.n_old);
+    const uint64_t cb = (uint64_t)a.per * a.item_len, total = a.n_new * a.item_len;
+    const uint64_t nch = (a.n_new + a.per - 1) / a.per;  // >= 2 (the host runs smaller lists through k_final_small)
+    uint64_t cnt = (nch + 1) >> 1, off = 0, capd = (a.cap_chunks + 1) >> 1;  // level d: nodes, offset, room
+    uint32_t d = 1;
+    uint32_t h[4];
+    if (T == 0) {  // nothing changed: the root again, from the stored top node
+        if (t != 0) return;
+        while (cnt > 1) {
+            off += capd;
+            capd = (capd + 1) >> 1;
+            cnt = (cnt + 1) >> 1;
+        }
+        lt_load_node(a.levels + 8 * off, 0, p, h);
+    } else {
+        if (t >= T) return;
+        uint64_t j = lt_chunk(a, t) >> 1;
+        if (t > 0 && (lt_chunk(a, t - 1) >> 1) == j) return;  // not the first work item of its level-1 node
+        uint64_t o = t, e = lt_upper(a, t + 1, T, 1, j);
+        {  // level-1 node j: bytes [2 j cb, min(total, (2 j + 2) cb)), then 0^128 when chunk 2 j + 1 is absent
+            const uint64_t b0 = 2 * j * cb;
+            const bool pad = 2 * j + 1 >= nch;
+            const uint64_t la = total - b0 < 2 * cb ? total - b0 : 2 * cb;
+            const uint8_t* src = a.items + b0;
+            if (la == 256 && !pad && (((uintptr_t)src) & 15u) == 0) {
+                hash_window3(reinterpret_cast<const uint4*>(src), p, h);
+            } else {
+                uint4 d0, d1;
+                sponge_generic(src, la, pad ? 128u : 0u, false, 0, d0, d1);
+                h[0] = ilv::to_ilv(d0.x, d0.y, p);
+                h[1] = ilv::to_ilv(d0.z, d0.w, p);
+                h[2] = ilv::to_ilv(d1.x, d1.y, p);
+                h[3] = ilv::to_ilv(d1.z, d1.w, p);
+            }
+        }
+        for (;;) {
+            uint32_t* lv = a.levels + 8 * off;
+            store_node3(lv, j, false, p, h);
+            if (cnt == 1) break;  // the top node
+            const uint64_t sib = j ^ 1u;
+            const bool right = (j & 1u) != 0;  // this node is the right child
+            bool sib_dirty;
+            if (right)
+                sib_dirty = o > 0 && (lt_chunk(a, o - 1) >> d) == sib;
+            else
+                sib_dirty = e < T && (lt_chunk(a, e) >> d) == sib;
+            if (sib_dirty) {
+                if (right)
+                    o = lt_lower(a, o - 1, d, sib);
+                else
+                    e = lt_upper(a, e + 1, T, d, sib);
+                __threadfence();  // release: this pair's node stores before its arrival
+                uint32_t second = 0;
+                if (p == 0) {
+                    const uint64_t old = __hip_atomic_fetch_or(a.arrive + o, 1ull << d, __ATOMIC_ACQ_REL,
+                                                               __HIP_MEMORY_SCOPE_AGENT);
+                    second = (uint32_t)(old >> d) & 1u;
+                }
+                second |= (uint32_t)__shfl_xor((int)second, 1);
+                if (!second) return;  // first to arrive: the sibling's pair hashes the parent
+                __threadfence();      // acquire: the sibling's stores before the loads below
+            }
+            uint32_t s[4] = {0u, 0u, 0u, 0u}, r[4];
+            const bool padded = sib >= cnt;  // only ever a missing RIGHT child
+            if (!padded) lt_load_node(lv, sib, p, s);
+            if (right)
+                hash_pair3(s, h, false, p, r);
+            else
+                hash_pair3(h, s, padded, p, r);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) h[w] = r[w];
+            j >>= 1;
+            off += capd;
+            capd = (capd + 1) >> 1;
+            cnt = (cnt + 1) >> 1;
+            ++d;
+        }
+    }
+    // root = K(top || le64(n) || 0^24) (hash.go:237-238)
+    uint32_t m[4] = {ilv::to_ilv((uint32_t)a.n_new, (uint32_t)(a.n_new >> 32), p), 0u, 0u, 0u}, r[4];
+    hash_pair3(h, m, false, p, r);
+    store_node3(a.root_out, 0, false, p, r);
+}
+
+// list[idx[v]] = values[v] for v < k_idx (an index >= n_old is skipped), then
+// the n_app appended values to items n_old ..; `unit`-byte pieces (8 when
+// everything is 8-B aligned, else 1), one per thread
+__global__ __launch_bounds__(256) void k_list_tree_scatter(uint8_t* __restrict__ items,
+                                                           const uint64_t* __restrict__ idx, uint64_t k_idx,
+                                                           uint64_t n_old, uint64_t n_app, uint32_t item_len,
+                                                           uint32_t unit, const uint8_t* __restrict__ vals) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t per = item_len / unit;
+    const uint64_t v = g / per;
+    const uint32_t w = (uint32_t)(g - v * per);
+    if (v >= k_idx + n_app) return;
+    const uint64_t x = v < k_idx ? idx[v] : n_old + (v - k_idx);
+    if (v < k_idx && x >= n_old) return;
+    const uint64_t src = v * item_len + (uint64_t)w * unit, dst = x * item_len + (uint64_t)w * unit;
+    if (unit == 8)
+        *reinterpret_cast<uint64_t*>(items + dst) = *reinterpret_cast<const uint64_t*>(vals + src);
+    else
+        items[dst] = vals[src];
+}
+
 }  // namespace mk

@@ -171,5 +171,22 @@ __global__ void k_many_level(const uint8_t* items, const ManyList* lists, const 
 __global__ void k_many_final(const uint8_t* items, const ManyList* lists, uint32_t nlists, const uint4* tops,
                              uint4* roots);
 __global__ void k_synth(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t word0);
+// device-resident list tree (merkle_kernels.hip, list_tree_api.cpp)
+struct ListTreeArgs {
+    const uint8_t* items;  // level 0: n_new items of item_len bytes
+    uint32_t* levels;      // level d >= 1 at node sum_{1<=i<d} ceil(cap_chunks / 2^i)
+    const uint64_t* idx;   // k_idx ascending dirty item indices < n_old (device)
+    uint64_t k_idx;
+    uint64_t n_old, n_new;  // items n_old .. n_new - 1 are appended (dirty)
+    uint64_t cap_chunks;
+    uint32_t item_len;
+    uint32_t per;          // items per chunk
+    uint64_t* arrive;      // one zeroed word per work item (k_idx + n_new - n_old)
+    uint32_t* root_out;
+};
+// one lane pair per dirty item; the ancestors of the dirty chunks and the root
+__global__ void k_list_tree_update(ListTreeArgs a);
+__global__ void k_list_tree_scatter(uint8_t* items, const uint64_t* idx, uint64_t k_idx, uint64_t n_old,
+                                    uint64_t n_app, uint32_t item_len, uint32_t unit, const uint8_t* vals);
 
 }  // namespace mk

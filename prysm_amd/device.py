@@ -485,6 +485,61 @@ def deposit_trie_branch(levels: torch.Tensor, capacity: int, count: int, depth: 
     return out
 
 
+def list_tree_levels_bytes(capacity: int, item_len: int) -> int:
+    """Bytes of the level array of a list tree with room for ``capacity`` items."""
+    return _lib.load().mk_ssz_list_tree_levels_bytes(capacity, item_len)
+
+
+def list_tree_update_workspace_bytes(k: int) -> int:
+    """Workspace of list_tree_update for k = changed + appended items."""
+    return _lib.load().mk_ssz_list_tree_update_workspace_bytes(k)
+
+
+def list_tree_build(items: torch.Tensor, n: int, capacity: int, item_len: int, levels: torch.Tensor,
+                    root: torch.Tensor = None, ws: torch.Tensor = None) -> torch.Tensor:
+    """Every level (into ``levels``) and the root of merkleHash over the n
+    items in ``items`` (hash.go:194-239), laid out for ``capacity`` items.
+    Returns the (32,) uint8 root tensor."""
+    dev = _dev(items)
+    if items.numel() * items.element_size() < n * item_len:
+        raise ValueError("item buffer shorter than n * item_len")
+    if levels.numel() < list_tree_levels_bytes(capacity, item_len):
+        raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, item_len)")
+    if root is None:
+        root = torch.empty(32, dtype=torch.uint8, device=items.device)
+    if ws is None:
+        ws = torch.empty(_lib.load().mk_ssz_list_tree_build_workspace_bytes(n, item_len), dtype=torch.uint8,
+                         device=items.device)
+    _lib.invoke("mk_dev_ssz_list_tree_build", _p(items), n, capacity, item_len, _p(levels), _p(root), _p(ws),
+                ws.numel(), _stream(items.device), device=dev)
+    return root
+
+
+def list_tree_update(items: torch.Tensor, n_old: int, n_new: int, capacity: int, item_len: int,
+                     levels: torch.Tensor, root: torch.Tensor, idx: torch.Tensor = None, k_idx: int = 0,
+                     values: torch.Tensor = None, ws: torch.Tensor = None) -> torch.Tensor:
+    """Re-hash a built list tree after ``k_idx`` items changed (``idx``:
+    ascending int64/uint64 device indices < n_old) and n_new - n_old were
+    appended: only the ancestors of the changed chunks.  ``values`` (the k_idx
+    new items, then the appended ones) are scattered into ``items`` first;
+    None: ``items`` already holds the new bytes.  Returns ``root``."""
+    dev = _dev(items)
+    if items.numel() * items.element_size() < n_new * item_len:
+        raise ValueError("item buffer shorter than n_new * item_len")
+    if k_idx and (idx is None or idx.numel() < k_idx or idx.element_size() != 8):
+        raise ValueError("idx: k_idx 64-bit device indices")
+    k = k_idx + max(n_new - n_old, 0)
+    if values is not None and values.numel() * values.element_size() < k * item_len:
+        raise ValueError("values shorter than (k_idx + appended) * item_len")
+    if ws is None:
+        ws = torch.empty(_lib.load().mk_ssz_list_tree_update_workspace_bytes(k), dtype=torch.uint8,
+                         device=items.device)
+    _lib.invoke("mk_dev_ssz_list_tree_update", _p(items), n_old, n_new, capacity, item_len, _p(levels),
+                _p(idx) if k_idx else None, k_idx, _p(values) if values is not None else None, _p(root), _p(ws),
+                ws.numel(), _stream(items.device), device=dev)
+    return root
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

@@ -1,0 +1,96 @@
+"""Host mirror of the device-resident list tree (``mk_list_tree_*``).
+
+``ssz.merkleHash`` (shared/ssz/hash.go:194-239) is one-shot: the whole list
+in, the root out.  A beacon node's long lists (the validator registry, the
+balances) live for the life of the process and change in a few places between
+two state roots.  ``ListTree`` keeps such a list and every level of its tree
+in HBM; ``update`` and ``append`` upload only the changed items and re-hash
+only the ancestors of the changed chunks, and ``root()`` always equals
+``merkleHash`` of the current items.  There is no CPU fallback.
+
+The registry composes with it without a struct kernel of its own: the list
+TreeHash hashes is the list of 32-B struct roots, so hash the ``k`` changed
+``ValidatorRecord``s with ``mk_dev_ssz_struct_roots`` and hand those roots to
+a 32-B-item tree::
+
+    tree = ListTree(32, capacity=n)
+    tree.assign(registry.struct_roots(reg.records))          # once
+    ...
+    changed = D.struct_roots(dev_records_of_the_k, k, 160, VALIDATOR_FIELDS)
+    tree.update(indices, changed.cpu().numpy())              # per state root
+    root = tree.root()
+
+(device-resident callers pass the roots as ``d_values`` of
+``device.list_tree_update`` and never leave the GPU).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .hashutil import _ptr
+
+
+class ListTree:
+    """A list of fixed-length items and its merkleHash tree, device-resident."""
+
+    def __init__(self, item_len: int, capacity: int = 0, device: int = -1):
+        self.item_len = int(item_len)
+        self._device = device
+        self._handle = None
+        h = ctypes.c_void_p()
+        _lib.invoke("mk_list_tree_new", self.item_len, int(capacity), ctypes.byref(h), device=device)
+        self._handle = h
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and _lib is not None:
+            try:
+                _lib.load().mk_list_tree_free(h)
+            except Exception:
+                pass
+
+    def __len__(self) -> int:
+        return int(_lib.load().mk_list_tree_count(self._handle))
+
+    def _flat(self, values) -> np.ndarray:
+        a = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1)
+        if a.size % self.item_len:
+            raise ValueError(f"{a.size} bytes are not a whole number of {self.item_len}-byte items")
+        return a
+
+    def assign(self, items) -> None:
+        """Replace the whole list (uint8 array of n * item_len bytes, any shape)."""
+        a = self._flat(items)
+        _lib.invoke("mk_list_tree_assign", self._handle, _ptr(a), a.size // self.item_len, device=self._device)
+
+    def update(self, indices, values) -> None:
+        """``list[indices[j]] = values[j]`` for every j in order (any order,
+        repeats allowed: the last value wins).  An index >= len(self) raises
+        and changes nothing."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        a = self._flat(values)
+        if a.size != idx.size * self.item_len:
+            raise ValueError("one item_len-byte value per index")
+        _lib.invoke("mk_list_tree_update", self._handle, _ptr(idx), _ptr(a), idx.size, device=self._device)
+
+    def append(self, items) -> None:
+        """Append items; past the capacity the tree doubles it and rebuilds."""
+        a = self._flat(items)
+        _lib.invoke("mk_list_tree_append", self._handle, _ptr(a), a.size // self.item_len, device=self._device)
+
+    def root(self) -> bytes:
+        """merkleHash of the current items."""
+        out = ctypes.create_string_buffer(32)
+        _lib.invoke("mk_list_tree_root", self._handle, out, device=self._device)
+        return out.raw
+
+    def items(self, first: int = 0, count: int = None) -> np.ndarray:
+        """Items [first, first + count) read back as a (count, item_len) uint8 array."""
+        if count is None:
+            count = len(self) - first
+        out = np.empty((max(count, 0), self.item_len), dtype=np.uint8)
+        _lib.invoke("mk_list_tree_items", self._handle, first, count, _ptr(out), device=self._device)
+        return out
