@@ -399,6 +399,72 @@ int mk_dev_ssz_struct_pipe_top(mk_call* call, const void* d_nodes, uint64_t n, u
                                uint32_t value_len, uint32_t which, void* d_levels, void* d_pair_block, uint32_t slot,
                                uint32_t epoch, void* d_ws, uint64_t ws_bytes, void* stream);
 
+/* ---- device-resident registry tree: a struct list re-hashed from changed records --- */
+/* TreeHash of a list of n flat records (mk_field layouts, see the struct
+ * hashing section above) with the records, their 32-B struct roots and every
+ * level of merkleHash over those roots kept in HBM: a changed or appended
+ * record costs its own struct hash and its ancestors instead of the whole
+ * registry, and one call owns records and roots, so they cannot drift apart.
+ * d_roots holds capacity x 32 B (16-B aligned) and is level 0 of a list tree
+ * of 32-B items: d_levels has exactly the layout and size of
+ * mk_ssz_list_tree_levels_bytes(capacity, 32) above (4 roots per chunk, a
+ * level-1 node covers 8 records); there is no second layout.  d_records is
+ * 4-byte aligned, capacity x record_len bytes.
+ * Every layout mk_dev_ssz_struct_roots accepts is taken.  An update gathers
+ * the dirty records, hashes them with the struct-roots kernels, scatters the
+ * roots into d_roots and climbs with the list tree's update kernel.
+ * Replaces: ssz.TreeHash of a []struct (makeSliceHasher, makeStructHasher and
+ * merkleHash, shared/ssz/hash.go:118-159, 194-239) for a list whose tree is
+ * already built. */
+uint64_t mk_ssz_struct_list_tree_build_workspace_bytes(uint64_t n, const mk_field* fields, uint32_t nfields);
+/* Every struct root (into d_roots), every level and the root of n <= capacity
+ * records.  A bad field spec is MK_EINVAL as in mk_dev_ssz_struct_roots. */
+int mk_dev_ssz_struct_list_tree_build(mk_call* call, const void* d_records, uint64_t n, uint64_t capacity,
+                                      uint32_t record_len, const mk_field* fields, uint32_t nfields, void* d_roots,
+                                      void* d_levels, void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream);
+/* Re-hash after a change, with the argument rules of
+ * mk_dev_ssz_list_tree_update: d_idx holds k_idx strictly ascending record
+ * indices < n_old (device memory), records [n_old, n_new) are appended.
+ * d_values != NULL (4-byte aligned): k_idx new records, then the appended
+ * ones, record_len bytes each, scattered into d_records first by the same
+ * call; NULL: the caller has already written them into d_records on this
+ * stream.  Recomputes the struct roots of exactly those records and their
+ * ancestors and writes the root to d_root32 (also when nothing changed; with
+ * n_new <= 4 the root is the mix-in over the raw chunk of roots).  An index >=
+ * n_old is ignored.  Workspace (8-B aligned) from
+ * mk_ssz_struct_list_tree_update_workspace_bytes(k, ..), k = k_idx + n_new -
+ * n_old (< 2^31): the call zeroes and owns it until it has run, so trees
+ * updated concurrently on different streams need a workspace each; too small
+ * is MK_ENOMEM.  n_new < n_old and n_new > capacity are MK_EINVAL.  Allocates
+ * nothing and can be captured into a hipGraph. */
+uint64_t mk_ssz_struct_list_tree_update_workspace_bytes(uint64_t k, const mk_field* fields, uint32_t nfields);
+int mk_dev_ssz_struct_list_tree_update(mk_call* call, void* d_records, uint64_t n_old, uint64_t n_new,
+                                       uint64_t capacity, uint32_t record_len, const mk_field* fields,
+                                       uint32_t nfields, void* d_roots, void* d_levels, const uint64_t* d_idx,
+                                       uint64_t k_idx, const void* d_values, void* d_root32, void* d_ws,
+                                       uint64_t ws_bytes, void* stream);
+/* Handle form for host callers (the validator registry): records, roots and
+ * levels stay in HBM under a per-handle lock, with mk_list_tree's semantics.
+ * update takes host indices in any order (list[idx[j]] = records[j] in
+ * sequence: of a repeated index the last value wins; an index >= count is
+ * MK_EINVAL and nothing changes) and uploads only the k indices and records;
+ * append past the capacity doubles it and rebuilds; a call that dirties a
+ * 1/32 of the list or more rebuilds instead of climbing.  The
+ * root of a new handle is merkleHash([]). */
+typedef struct mk_struct_list_tree mk_struct_list_tree;
+int mk_struct_list_tree_new(mk_call* call, uint32_t record_len, const mk_field* fields, uint32_t nfields,
+                            uint64_t capacity, mk_struct_list_tree** out);
+void mk_struct_list_tree_free(mk_struct_list_tree* t);
+uint64_t mk_struct_list_tree_count(const mk_struct_list_tree* t);
+/* Replaces the whole list by n records. */
+int mk_struct_list_tree_assign(mk_call* call, mk_struct_list_tree* t, const uint8_t* records, uint64_t n);
+int mk_struct_list_tree_update(mk_call* call, mk_struct_list_tree* t, const uint64_t* idx, const uint8_t* records,
+                               uint64_t k);
+int mk_struct_list_tree_append(mk_call* call, mk_struct_list_tree* t, const uint8_t* records, uint64_t k);
+int mk_struct_list_tree_root(mk_call* call, mk_struct_list_tree* t, uint8_t root[32]);
+/* Records [first, first + cnt), cnt x record_len bytes. */
+int mk_struct_list_tree_records(mk_call* call, mk_struct_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

@@ -280,6 +280,22 @@ int tree_items(mk_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out) {
 
 }  // namespace
 
+// what the registry tree (struct_tree_api.cpp) runs over its buffer of 32-B struct roots
+namespace mk::rt {
+int list_tree_build32(const void* d_roots, uint64_t n, uint64_t capacity, void* d_levels, void* d_root32, void* d_ws,
+                      hipStream_t st) {
+    return dev_build(d_roots, n, capacity, 32, d_levels, d_root32, d_ws, st);
+}
+int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
+                       uint64_t n_new, uint64_t capacity, void* d_root32, void* d_ws, hipStream_t st) {
+    return launch_update(d_roots, d_levels, d_idx, k_idx, n_old, n_new, capacity, 32, d_root32, d_ws, st);
+}
+int list_tree_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
+                      uint32_t item_len, const void* d_values, hipStream_t st) {
+    return launch_scatter(d_items, d_idx, k_idx, n_old, n_app, item_len, d_values, st);
+}
+}  // namespace mk::rt
+
 extern "C" {
 
 uint64_t mk_ssz_list_tree_levels_bytes(uint64_t capacity, uint32_t item_len) {

@@ -4244,4 +4244,33 @@ __global__ __launch_bounds__(256) void k_list_tree_scatter(uint8_t* __restrict__
         items[dst] = vals[src];
 }
 
+// ----------------------------------------------------------------------------
+// Device-resident registry tree: TreeHash of a list of flat
+// structs (hash.go:118-159, 194-239) re-hashed from the changed RECORDS.  The
+// tree is the list tree above over the buffer of 32-B struct roots; an update
+// gathers the dirty records, hashes them with the struct-roots kernels,
+// scatters the roots (k_list_tree_scatter) and climbs (k_list_tree_update).
+// The gather: the first `ext` bytes (a multiple of 4) of the record of every
+// work item (idx[t] clamped to the last old record as in lt_chunk, then the
+// appended records) to out + t * ext, one dword per thread
+__global__ __launch_bounds__(256) void k_struct_tree_gather(const uint8_t* __restrict__ rec,
+                                                            const uint64_t* __restrict__ idx, uint64_t k_idx,
+                                                            uint64_t n_old, uint64_t n_app, uint32_t rec_len,
+                                                            uint32_t ext, uint8_t* __restrict__ out) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t per = ext / 4;
+    const uint64_t t = g / per;
+    const uint32_t w = (uint32_t)(g - t * per);
+    if (t >= k_idx + n_app) return;
+    uint64_t x;
+    if (t < k_idx) {
+        x = idx[t];
+        const uint64_t last = n_old ? n_old - 1 : 0;
+        if (x > last) x = last;
+    } else {
+        x = n_old + (t - k_idx);
+    }
+    reinterpret_cast<uint32_t*>(out + t * ext)[w] = reinterpret_cast<const uint32_t*>(rec + x * rec_len)[w];
+}
+
 }  // namespace mk

@@ -188,5 +188,8 @@ struct ListTreeArgs {
 __global__ void k_list_tree_update(ListTreeArgs a);
 __global__ void k_list_tree_scatter(uint8_t* items, const uint64_t* idx, uint64_t k_idx, uint64_t n_old,
                                     uint64_t n_app, uint32_t item_len, uint32_t unit, const uint8_t* vals);
+// device-resident registry tree (struct_tree_api.cpp): the dirty records side by side
+__global__ void k_struct_tree_gather(const uint8_t* rec, const uint64_t* idx, uint64_t k_idx, uint64_t n_old,
+                                     uint64_t n_app, uint32_t rec_len, uint32_t ext, uint8_t* out);
 
 }  // namespace mk

@@ -158,6 +158,21 @@ int host_merkle_hash_plain(const uint8_t* items, uint64_t n, uint32_t item_len, 
 uint32_t next_arrive_slots(uint32_t k);
 uint32_t top_arrive_slots(uint64_t parts);
 
+// ---- flat records (struct_api.cpp) ------------------------------------------------
+int struct_make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::StructSpec& sp);
+bool struct_fused_layout(const mk::StructSpec& sp);  // a layout k_struct_fused takes (4-B aligned records)
+// roots of n records into d_roots (n x 32); d_msg: n x msg_len bytes (unused for a fused layout)
+int struct_launch_roots(const void* d_rec, uint64_t n, const mk::StructSpec& sp, void* d_msg, void* d_roots,
+                        hipStream_t st);
+
+// ---- list tree over 32-B items (list_tree_api.cpp) -----------------------------------
+int list_tree_build32(const void* d_roots, uint64_t n, uint64_t capacity, void* d_levels, void* d_root32, void* d_ws,
+                      hipStream_t st);  // d_ws: 256 B
+int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
+                       uint64_t n_new, uint64_t capacity, void* d_root32, void* d_ws, hipStream_t st);  // > 4 items
+int list_tree_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
+                      uint32_t item_len, const void* d_values, hipStream_t st);
+
 // ---- multi-device (multi_api.cpp) ------------------------------------------------
 int host_merkle_multi(const uint8_t* items, uint64_t n, uint32_t item_len, int nshards, const int* devs_in,
                       uint8_t* out, uint32_t elem_len = 0);

@@ -344,6 +344,18 @@ int host_struct_list_root(const uint8_t* records, uint64_t n, uint32_t record_le
 
 }  // namespace
 
+// what the registry tree (struct_tree_api.cpp) takes from here
+namespace mk::rt {
+int struct_make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::StructSpec& sp) {
+    return make_spec(fields, nfields, record_len, sp);
+}
+bool struct_fused_layout(const mk::StructSpec& sp) { return struct_form(nullptr, 0, sp).fused; }
+int struct_launch_roots(const void* d_rec, uint64_t n, const mk::StructSpec& sp, void* d_msg, void* d_roots,
+                        hipStream_t st) {
+    return launch_struct_roots(d_rec, n, sp, d_msg, d_roots, st);
+}
+}  // namespace mk::rt
+
 extern "C" {
 
 // ---- struct hashing ---------------------------------------------------------------

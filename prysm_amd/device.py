@@ -540,6 +540,73 @@ def list_tree_update(items: torch.Tensor, n_old: int, n_new: int, capacity: int,
     return root
 
 
+def struct_list_tree_build_workspace_bytes(n: int, spec) -> int:
+    from .registry import _fields
+
+    return _lib.load().mk_ssz_struct_list_tree_build_workspace_bytes(n, _fields(spec), len(spec))
+
+
+def struct_list_tree_update_workspace_bytes(k: int, spec) -> int:
+    """Workspace of struct_list_tree_update for k = changed + appended records."""
+    from .registry import _fields
+
+    return _lib.load().mk_ssz_struct_list_tree_update_workspace_bytes(k, _fields(spec), len(spec))
+
+
+def struct_list_tree_build(records: torch.Tensor, n: int, capacity: int, record_len: int, spec,
+                           roots: torch.Tensor, levels: torch.Tensor, root: torch.Tensor = None,
+                           ws: torch.Tensor = None) -> torch.Tensor:
+    """Every struct root (into ``roots``, capacity x 32 B), every level (into
+    ``levels``, the layout of ``list_tree_levels_bytes(capacity, 32)``) and the
+    root of TreeHash over the n records in ``records`` (hash.go:118-159,
+    194-239).  Returns the (32,) uint8 root tensor."""
+    from .registry import _fields
+
+    dev = _dev(records)
+    if records.numel() * records.element_size() < n * record_len:
+        raise ValueError("record buffer shorter than n * record_len")
+    if roots.numel() < 32 * capacity:
+        raise ValueError("roots buffer shorter than 32 * capacity")
+    if levels.numel() < list_tree_levels_bytes(capacity, 32):
+        raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, 32)")
+    if root is None:
+        root = torch.empty(32, dtype=torch.uint8, device=records.device)
+    if ws is None:
+        ws = torch.empty(struct_list_tree_build_workspace_bytes(n, spec), dtype=torch.uint8, device=records.device)
+    _lib.invoke("mk_dev_ssz_struct_list_tree_build", _p(records), n, capacity, record_len, _fields(spec), len(spec),
+                _p(roots), _p(levels), _p(root), _p(ws), ws.numel(), _stream(records.device), device=dev)
+    return root
+
+
+def struct_list_tree_update(records: torch.Tensor, n_old: int, n_new: int, capacity: int, record_len: int, spec,
+                            roots: torch.Tensor, levels: torch.Tensor, root: torch.Tensor,
+                            idx: torch.Tensor = None, k_idx: int = 0, values: torch.Tensor = None,
+                            ws: torch.Tensor = None) -> torch.Tensor:
+    """Re-hash a built registry tree after ``k_idx`` records changed (``idx``:
+    ascending int64/uint64 device indices < n_old) and n_new - n_old were
+    appended: those records' struct roots and their ancestors only.
+    ``values`` (the k_idx new records, then the appended ones) are scattered
+    into ``records`` first; None: ``records`` already holds them.  Returns
+    ``root``."""
+    from .registry import _fields
+
+    dev = _dev(records)
+    if records.numel() * records.element_size() < n_new * record_len:
+        raise ValueError("record buffer shorter than n_new * record_len")
+    if k_idx and (idx is None or idx.numel() < k_idx or idx.element_size() != 8):
+        raise ValueError("idx: k_idx 64-bit device indices")
+    k = k_idx + max(n_new - n_old, 0)
+    if values is not None and values.numel() * values.element_size() < k * record_len:
+        raise ValueError("values shorter than (k_idx + appended) * record_len")
+    if ws is None:
+        ws = torch.empty(struct_list_tree_update_workspace_bytes(k, spec), dtype=torch.uint8, device=records.device)
+    _lib.invoke("mk_dev_ssz_struct_list_tree_update", _p(records), n_old, n_new, capacity, record_len, _fields(spec),
+                len(spec), _p(roots), _p(levels), _p(idx) if k_idx else None, k_idx,
+                _p(values) if values is not None else None, _p(root), _p(ws), ws.numel(), _stream(records.device),
+                device=dev)
+    return root
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

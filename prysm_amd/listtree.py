@@ -8,20 +8,22 @@ in HBM; ``update`` and ``append`` upload only the changed items and re-hash
 only the ancestors of the changed chunks, and ``root()`` always equals
 ``merkleHash`` of the current items.  There is no CPU fallback.
 
-The registry composes with it without a struct kernel of its own: the list
-TreeHash hashes is the list of 32-B struct roots, so hash the ``k`` changed
-``ValidatorRecord``s with ``mk_dev_ssz_struct_roots`` and hand those roots to
-a 32-B-item tree::
+A list of STRUCTS (the validator registry itself) has a handle of its own,
+``StructListTree`` (``mk_struct_list_tree_*``): it owns the
+records as well as their 32-B struct roots and the levels over them, so a
+changed ``ValidatorRecord`` goes in as a record and costs its own struct hash
+plus its ancestors::
 
-    tree = ListTree(32, capacity=n)
-    tree.assign(registry.struct_roots(reg.records))          # once
+    tree = StructListTree(160, VALIDATOR_FIELDS, capacity=n)
+    tree.assign(reg.records)                                  # once
     ...
-    changed = D.struct_roots(dev_records_of_the_k, k, 160, VALIDATOR_FIELDS)
-    tree.update(indices, changed.cpu().numpy())              # per state root
-    root = tree.root()
+    tree.update(indices, changed_records)                     # per state root
+    root = tree.root()           # == registry.struct_list_root(all records)
 
-(device-resident callers pass the roots as ``d_values`` of
-``device.list_tree_update`` and never leave the GPU).
+(device-resident callers use ``device.struct_list_tree_build`` /
+``struct_list_tree_update`` and never leave the GPU;
+``registry.ResidentState`` pairs the registry with a ``ListTree(8)`` of the
+balances and returns the State root).
 """
 from __future__ import annotations
 
@@ -93,4 +95,75 @@ class ListTree:
             count = len(self) - first
         out = np.empty((max(count, 0), self.item_len), dtype=np.uint8)
         _lib.invoke("mk_list_tree_items", self._handle, first, count, _ptr(out), device=self._device)
+        return out
+
+
+class StructListTree:
+    """A list of flat fixed-layout records (``fields`` = [(kind, offset, len)]
+    as in ``registry.VALIDATOR_FIELDS``) and the tree of its TreeHash,
+    device-resident: records, struct roots and levels."""
+
+    def __init__(self, record_len: int, fields, capacity: int = 0, device: int = -1):
+        from .registry import _fields
+
+        self.record_len = int(record_len)
+        self.fields = list(fields)
+        self._device = device
+        self._handle = None
+        h = ctypes.c_void_p()
+        _lib.invoke("mk_struct_list_tree_new", self.record_len, _fields(self.fields), len(self.fields),
+                    int(capacity), ctypes.byref(h), device=device)
+        self._handle = h
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and _lib is not None:
+            try:
+                _lib.load().mk_struct_list_tree_free(h)
+            except Exception:
+                pass
+
+    def __len__(self) -> int:
+        return int(_lib.load().mk_struct_list_tree_count(self._handle))
+
+    def _flat(self, records) -> np.ndarray:
+        a = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        if a.size % self.record_len:
+            raise ValueError(f"{a.size} bytes are not a whole number of {self.record_len}-byte records")
+        return a
+
+    def assign(self, records) -> None:
+        """Replace the whole list (n records: a structured or uint8 array)."""
+        a = self._flat(records)
+        _lib.invoke("mk_struct_list_tree_assign", self._handle, _ptr(a), a.size // self.record_len,
+                    device=self._device)
+
+    def update(self, indices, records) -> None:
+        """``list[indices[j]] = records[j]`` for every j in order (any order,
+        repeats allowed: the last value wins).  An index >= len(self) raises
+        and changes nothing."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        a = self._flat(records)
+        if a.size != idx.size * self.record_len:
+            raise ValueError("one record per index")
+        _lib.invoke("mk_struct_list_tree_update", self._handle, _ptr(idx), _ptr(a), idx.size, device=self._device)
+
+    def append(self, records) -> None:
+        """Append records; past the capacity the tree doubles it and rebuilds."""
+        a = self._flat(records)
+        _lib.invoke("mk_struct_list_tree_append", self._handle, _ptr(a), a.size // self.record_len,
+                    device=self._device)
+
+    def root(self) -> bytes:
+        """TreeHash of the current list of records."""
+        out = ctypes.create_string_buffer(32)
+        _lib.invoke("mk_struct_list_tree_root", self._handle, out, device=self._device)
+        return out.raw
+
+    def records(self, first: int = 0, count: int = None) -> np.ndarray:
+        """Records [first, first + count) read back as a (count, record_len) uint8 array."""
+        if count is None:
+            count = len(self) - first
+        out = np.empty((max(count, 0), self.record_len), dtype=np.uint8)
+        _lib.invoke("mk_struct_list_tree_records", self._handle, first, count, _ptr(out), device=self._device)
         return out

@@ -120,6 +120,52 @@ def state_root(registry: ValidatorRegistry, balances: np.ndarray) -> bytes:
     return hash_batch_var([reg + bal_root])[0]
 
 
+class ResidentState:
+    """State{ValidatorRegistry, ValidatorBalances} kept in HBM between state
+    roots: a ``listtree.StructListTree`` owns the records, a ``ListTree(8)``
+    the balances.  Changed or appended validators and balances go in;
+    ``root()`` is what ``state_root`` returns for the same content, at the
+    cost of the changed records' struct hashes and their ancestors
+    (DESIGN.md §5e)."""
+
+    def __init__(self, capacity: int = 0, device: int = -1):
+        from .listtree import ListTree, StructListTree
+
+        self.validators = StructListTree(VALIDATOR_DTYPE.itemsize, VALIDATOR_FIELDS, capacity, device)
+        self.balances = ListTree(8, capacity, device)
+
+    def __len__(self):
+        return len(self.validators)
+
+    @staticmethod
+    def _bal(values) -> np.ndarray:
+        return np.ascontiguousarray(values, dtype="<u8").view(np.uint8)
+
+    def assign(self, records: np.ndarray, balances: np.ndarray) -> None:
+        if len(records) != len(balances):
+            raise ValueError("one balance per validator")
+        self.validators.assign(records)
+        self.balances.assign(self._bal(balances))
+
+    def update_validators(self, idx, records: np.ndarray) -> None:
+        self.validators.update(idx, records)
+
+    def update_balances(self, idx, values) -> None:
+        self.balances.update(idx, self._bal(values))
+
+    def append(self, records: np.ndarray, balances: np.ndarray) -> None:
+        if len(records) != len(balances):
+            raise ValueError("one balance per validator")
+        self.validators.append(records)
+        self.balances.append(self._bal(balances))
+
+    def root(self) -> bytes:
+        """Keccak(registry_root || balances_root), the 64-B hash by the library."""
+        from .hashutil import hash_batch_var
+
+        return hash_batch_var([self.validators.root() + self.balances.root()])[0]
+
+
 class DeviceStateHasher:
     """TreeHash of State{ValidatorRegistry, ValidatorBalances} from records and
     balances resident in HBM (BASELINE config 3, device-resident), with every
