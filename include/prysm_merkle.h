@@ -465,6 +465,72 @@ int mk_struct_list_tree_root(mk_call* call, mk_struct_list_tree* t, uint8_t root
 /* Records [first, first + cnt), cnt x record_len bytes. */
 int mk_struct_list_tree_records(mk_call* call, mk_struct_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
 
+/* ---- device-resident bytes tree: a [][N]byte list re-hashed from changed elements --- */
+/* TreeHash of a list of n byte strings of elem_len bytes each (1 .. 2^30; the
+ * list mk_dev_ssz_tree_hash_bytes_list hashes in one shot) with the elements,
+ * their 32-B digests K(le32(elem_len) || e_i) and every level of merkleHash
+ * over those digests kept in HBM: a changed or appended element costs its own
+ * digest and the ancestors of its chunk instead of the whole list, and one
+ * call owns elements and digests, so they cannot drift apart.
+ * d_digests holds capacity x 32 B (16-B aligned) and is level 0 of a list tree
+ * of 32-B items: d_levels has exactly the layout and size of
+ * mk_ssz_list_tree_levels_bytes(capacity, 32) above (4 digests per chunk, a
+ * level-1 node covers 8 elements); there is no second layout.  d_elems is
+ * capacity x elem_len bytes, flat, at any byte alignment (32-B elements at a
+ * 16-B aligned base take the one-permutation digest).  elem_len == 0 is
+ * MK_EINVAL here (the one-shot entry keeps accepting it); a list whose
+ * elements differ in length is not covered.
+ * Replaces: ssz.TreeHash of a [][N]byte (makeSliceHasher, hashedEncoding and
+ * merkleHash, shared/ssz/hash.go:100-107, 118-139, 194-239) for a list whose
+ * tree is already built. */
+uint64_t mk_ssz_bytes_list_tree_build_workspace_bytes(uint64_t n, uint32_t elem_len);
+/* Every element digest (into d_digests), every level and the root of
+ * n <= capacity elements. */
+int mk_dev_ssz_bytes_list_tree_build(mk_call* call, const void* d_elems, uint64_t n, uint64_t capacity,
+                                     uint32_t elem_len, void* d_digests, void* d_levels, void* d_root32, void* d_ws,
+                                     uint64_t ws_bytes, void* stream);
+/* Re-hash after a change, with the argument rules of
+ * mk_dev_ssz_struct_list_tree_update: d_idx holds k_idx strictly ascending
+ * element indices < n_old (device memory), elements [n_old, n_new) are
+ * appended.  d_values != NULL: k_idx new elements, then the appended ones,
+ * elem_len bytes each, scattered into d_elems first by the same call; NULL:
+ * the caller has already written them into d_elems on this stream.
+ * Recomputes the digests of exactly those elements (read in place, no
+ * gathered copy) and their ancestors and writes the root to d_root32 (also
+ * when nothing changed; with n_new <= 4 the root is the mix-in over the raw
+ * chunk of digests).  An index >= n_old is ignored.  Workspace (8-B aligned)
+ * from mk_ssz_bytes_list_tree_update_workspace_bytes(k, elem_len), k = k_idx +
+ * n_new - n_old (< 2^31): the call zeroes and owns it until it has run, so
+ * trees updated concurrently on different streams need a workspace each; too
+ * small is MK_ENOMEM.  n_new < n_old, n_new > capacity and elem_len == 0 are
+ * MK_EINVAL; these checks come before any device lookup.  Allocates nothing
+ * and can be captured into a hipGraph. */
+uint64_t mk_ssz_bytes_list_tree_update_workspace_bytes(uint64_t k, uint32_t elem_len);
+int mk_dev_ssz_bytes_list_tree_update(mk_call* call, void* d_elems, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                                      uint32_t elem_len, void* d_digests, void* d_levels, const uint64_t* d_idx,
+                                      uint64_t k_idx, const void* d_values, void* d_root32, void* d_ws,
+                                      uint64_t ws_bytes, void* stream);
+/* Handle form for host callers (the state's root arrays): elements, digests
+ * and levels stay in HBM under a per-handle lock, with mk_struct_list_tree's
+ * semantics.  update takes host indices in any order (list[idx[j]] = elems[j]
+ * in sequence: of a repeated index the last value wins; an index >= count is
+ * MK_EINVAL and nothing changes) and uploads only the k indices and elements;
+ * append past the capacity doubles it and rebuilds; a call that dirties a
+ * 1/256 of the list or more rebuilds instead of climbing.  The
+ * root of a new handle is merkleHash([]). */
+typedef struct mk_bytes_list_tree mk_bytes_list_tree;
+int mk_bytes_list_tree_new(mk_call* call, uint32_t elem_len, uint64_t capacity, mk_bytes_list_tree** out);
+void mk_bytes_list_tree_free(mk_bytes_list_tree* t);
+uint64_t mk_bytes_list_tree_count(const mk_bytes_list_tree* t);
+/* Replaces the whole list by n elements. */
+int mk_bytes_list_tree_assign(mk_call* call, mk_bytes_list_tree* t, const uint8_t* elems, uint64_t n);
+int mk_bytes_list_tree_update(mk_call* call, mk_bytes_list_tree* t, const uint64_t* idx, const uint8_t* elems,
+                              uint64_t k);
+int mk_bytes_list_tree_append(mk_call* call, mk_bytes_list_tree* t, const uint8_t* elems, uint64_t k);
+int mk_bytes_list_tree_root(mk_call* call, mk_bytes_list_tree* t, uint8_t root[32]);
+/* Elements [first, first + cnt), cnt x elem_len bytes. */
+int mk_bytes_list_tree_elems(mk_call* call, mk_bytes_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

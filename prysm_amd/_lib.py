@@ -139,6 +139,19 @@ _SIGS = {
     "mk_struct_list_tree_append": (_int, [_cp, _vp, _vp, _u64]),
     "mk_struct_list_tree_root": (_int, [_cp, _vp, _vp]),
     "mk_struct_list_tree_records": (_int, [_cp, _vp, _u64, _u64, _vp]),
+    "mk_ssz_bytes_list_tree_build_workspace_bytes": (_u64, [_u64, _u32]),
+    "mk_dev_ssz_bytes_list_tree_build": (_int, [_cp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "mk_ssz_bytes_list_tree_update_workspace_bytes": (_u64, [_u64, _u32]),
+    "mk_dev_ssz_bytes_list_tree_update": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp,
+                                                 _vp, _u64, _vp]),
+    "mk_bytes_list_tree_new": (_int, [_cp, _u32, _u64, _vp]),
+    "mk_bytes_list_tree_free": (None, [_vp]),
+    "mk_bytes_list_tree_count": (_u64, [_vp]),
+    "mk_bytes_list_tree_assign": (_int, [_cp, _vp, _vp, _u64]),
+    "mk_bytes_list_tree_update": (_int, [_cp, _vp, _vp, _vp, _u64]),
+    "mk_bytes_list_tree_append": (_int, [_cp, _vp, _vp, _u64]),
+    "mk_bytes_list_tree_root": (_int, [_cp, _vp, _vp]),
+    "mk_bytes_list_tree_elems": (_int, [_cp, _vp, _u64, _u64, _vp]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),

@@ -4273,4 +4273,37 @@ __global__ __launch_bounds__(256) void k_struct_tree_gather(const uint8_t* __res
     reinterpret_cast<uint32_t*>(out + t * ext)[w] = reinterpret_cast<const uint32_t*>(rec + x * rec_len)[w];
 }
 
+// ----------------------------------------------------------------------------
+// Device-resident tree of a list of byte strings: TreeHash of
+// a [][N]byte (hash.go:100-107, 118-139, 194-239) re-hashed from the changed
+// ELEMENTS.  The tree is the list tree above over the buffer of 32-B element
+// digests K(le32(elem_len) || e_i); an update digests the dirty elements in
+// place (this kernel) and climbs (k_list_tree_update).
+// One thread per work item (the listed indices, then the appended elements,
+// as in lt_chunk) reads its element from `elems` and stores the digest at
+// digests[index]; a listed index >= n_old writes nothing.  fast32: 32-B
+// elements at a 16-B aligned base (elem32_digest, one block), otherwise the
+// general sponge of k_elem_digests<false>.
+__global__ __launch_bounds__(256) void k_bytes_tree_digest(const uint8_t* __restrict__ elems, uint32_t elem_len,
+                                                           uint32_t fast32, const uint64_t* __restrict__ idx,
+                                                           uint64_t k_idx, uint64_t n_old, uint64_t n_app,
+                                                           uint4* __restrict__ digests) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= k_idx + n_app) return;
+    uint64_t x;
+    if (w < k_idx) {
+        x = idx[w];
+        if (x >= n_old) return;
+    } else {
+        x = n_old + (w - k_idx);
+    }
+    uint32_t d[8];
+    if (fast32)
+        elem32_digest(reinterpret_cast<const uint4*>(elems) + 2 * x, d);
+    else
+        elem_digest_any(elems + x * (uint64_t)elem_len, elem_len, d);
+    digests[2 * x] = make_uint4(d[0], d[1], d[2], d[3]);
+    digests[2 * x + 1] = make_uint4(d[4], d[5], d[6], d[7]);
+}
+
 }  // namespace mk

@@ -192,4 +192,9 @@ __global__ void k_list_tree_scatter(uint8_t* items, const uint64_t* idx, uint64_
 __global__ void k_struct_tree_gather(const uint8_t* rec, const uint64_t* idx, uint64_t k_idx, uint64_t n_old,
                                      uint64_t n_app, uint32_t rec_len, uint32_t ext, uint8_t* out);
 
+// device-resident tree of a list of byte strings (bytes_tree_api.cpp): the digests of the dirty
+// elements, read in place, into the tree's level 0 (fast32: 32-B elements at a 16-B aligned base)
+__global__ void k_bytes_tree_digest(const uint8_t* elems, uint32_t elem_len, uint32_t fast32, const uint64_t* idx,
+                                    uint64_t k_idx, uint64_t n_old, uint64_t n_app, uint4* digests);
+
 }  // namespace mk

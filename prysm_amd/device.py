@@ -607,6 +607,65 @@ def struct_list_tree_update(records: torch.Tensor, n_old: int, n_new: int, capac
     return root
 
 
+def bytes_list_tree_build_workspace_bytes(n: int, elem_len: int) -> int:
+    return _lib.load().mk_ssz_bytes_list_tree_build_workspace_bytes(n, elem_len)
+
+
+def bytes_list_tree_update_workspace_bytes(k: int, elem_len: int) -> int:
+    """Workspace of bytes_list_tree_update for k = changed + appended elements."""
+    return _lib.load().mk_ssz_bytes_list_tree_update_workspace_bytes(k, elem_len)
+
+
+def bytes_list_tree_build(elems: torch.Tensor, n: int, capacity: int, elem_len: int, digests: torch.Tensor,
+                          levels: torch.Tensor, root: torch.Tensor = None, ws: torch.Tensor = None) -> torch.Tensor:
+    """Every element digest K(le32(elem_len) || e_i) (into ``digests``,
+    capacity x 32 B), every level (into ``levels``, the layout of
+    ``list_tree_levels_bytes(capacity, 32)``) and the root of TreeHash over the
+    n byte strings in ``elems`` (hash.go:100-107, 118-139, 194-239).  Returns
+    the (32,) uint8 root tensor."""
+    dev = _dev(elems)
+    if elems.numel() * elems.element_size() < n * elem_len:
+        raise ValueError("element buffer shorter than n * elem_len")
+    if digests.numel() < 32 * capacity:
+        raise ValueError("digest buffer shorter than 32 * capacity")
+    if levels.numel() < list_tree_levels_bytes(capacity, 32):
+        raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, 32)")
+    if root is None:
+        root = torch.empty(32, dtype=torch.uint8, device=elems.device)
+    if ws is None:
+        ws = torch.empty(bytes_list_tree_build_workspace_bytes(n, elem_len), dtype=torch.uint8, device=elems.device)
+    _lib.invoke("mk_dev_ssz_bytes_list_tree_build", _p(elems), n, capacity, elem_len, _p(digests), _p(levels),
+                _p(root), _p(ws), ws.numel(), _stream(elems.device), device=dev)
+    return root
+
+
+def bytes_list_tree_update(elems: torch.Tensor, n_old: int, n_new: int, capacity: int, elem_len: int,
+                           digests: torch.Tensor, levels: torch.Tensor, root: torch.Tensor,
+                           idx: torch.Tensor = None, k_idx: int = 0, values: torch.Tensor = None,
+                           ws: torch.Tensor = None) -> torch.Tensor:
+    """Re-hash a built bytes tree after ``k_idx`` elements changed (``idx``:
+    ascending int64/uint64 device indices < n_old) and n_new - n_old were
+    appended: those elements' digests and their ancestors only.  ``values``
+    (the k_idx new elements, then the appended ones) are scattered into
+    ``elems`` first; None: ``elems`` already holds them.  Returns ``root``."""
+    dev = _dev(elems)
+    if elems.numel() * elems.element_size() < n_new * elem_len:
+        raise ValueError("element buffer shorter than n_new * elem_len")
+    if digests.numel() < 32 * n_new:
+        raise ValueError("digest buffer shorter than 32 * n_new")
+    if k_idx and (idx is None or idx.numel() < k_idx or idx.element_size() != 8):
+        raise ValueError("idx: k_idx 64-bit device indices")
+    k = k_idx + max(n_new - n_old, 0)
+    if values is not None and values.numel() * values.element_size() < k * elem_len:
+        raise ValueError("values shorter than (k_idx + appended) * elem_len")
+    if ws is None:
+        ws = torch.empty(bytes_list_tree_update_workspace_bytes(k, elem_len), dtype=torch.uint8, device=elems.device)
+    _lib.invoke("mk_dev_ssz_bytes_list_tree_update", _p(elems), n_old, n_new, capacity, elem_len, _p(digests),
+                _p(levels), _p(idx) if k_idx else None, k_idx, _p(values) if values is not None else None, _p(root),
+                _p(ws), ws.numel(), _stream(elems.device), device=dev)
+    return root
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

@@ -24,6 +24,16 @@ plus its ancestors::
 ``struct_list_tree_update`` and never leave the GPU;
 ``registry.ResidentState`` pairs the registry with a ``ListTree(8)`` of the
 balances and returns the State root).
+
+A list of BYTE STRINGS (``[][N]byte``: the state's randao mixes, block roots
+and index roots, where one element changes per slot) has ``BytesListTree``
+(``mk_bytes_list_tree_*``): it owns the elements, their digests
+``K(le32(N) || e_i)`` and the levels over them::
+
+    tree = BytesListTree(32, capacity=8192)
+    tree.assign(block_roots)                                  # once
+    tree.update([slot % 8192], new_root)                      # per slot
+    root = tree.root()           # == ssz.tree_hash_bytes_list(all elements)
 """
 from __future__ import annotations
 
@@ -166,4 +176,71 @@ class StructListTree:
             count = len(self) - first
         out = np.empty((max(count, 0), self.record_len), dtype=np.uint8)
         _lib.invoke("mk_struct_list_tree_records", self._handle, first, count, _ptr(out), device=self._device)
+        return out
+
+
+class BytesListTree:
+    """A list of byte strings of ``elem_len`` bytes each (``[][N]byte``) and
+    the tree of its TreeHash, device-resident: elements, element digests and
+    levels."""
+
+    def __init__(self, elem_len: int, capacity: int = 0, device: int = -1):
+        self.elem_len = int(elem_len)
+        self._device = device
+        self._handle = None
+        h = ctypes.c_void_p()
+        _lib.invoke("mk_bytes_list_tree_new", self.elem_len, int(capacity), ctypes.byref(h), device=device)
+        self._handle = h
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and _lib is not None:
+            try:
+                _lib.load().mk_bytes_list_tree_free(h)
+            except Exception:
+                pass
+
+    def __len__(self) -> int:
+        return int(_lib.load().mk_bytes_list_tree_count(self._handle))
+
+    def _flat(self, elems) -> np.ndarray:
+        a = np.ascontiguousarray(elems, dtype=np.uint8).reshape(-1)
+        if a.size % self.elem_len:
+            raise ValueError(f"{a.size} bytes are not a whole number of {self.elem_len}-byte elements")
+        return a
+
+    def assign(self, elems) -> None:
+        """Replace the whole list (uint8 array of n * elem_len bytes, any shape)."""
+        a = self._flat(elems)
+        _lib.invoke("mk_bytes_list_tree_assign", self._handle, _ptr(a), a.size // self.elem_len,
+                    device=self._device)
+
+    def update(self, indices, elems) -> None:
+        """``list[indices[j]] = elems[j]`` for every j in order (any order,
+        repeats allowed: the last value wins).  An index >= len(self) raises
+        and changes nothing."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        a = self._flat(elems)
+        if a.size != idx.size * self.elem_len:
+            raise ValueError("one elem_len-byte element per index")
+        _lib.invoke("mk_bytes_list_tree_update", self._handle, _ptr(idx), _ptr(a), idx.size, device=self._device)
+
+    def append(self, elems) -> None:
+        """Append elements; past the capacity the tree doubles it and rebuilds."""
+        a = self._flat(elems)
+        _lib.invoke("mk_bytes_list_tree_append", self._handle, _ptr(a), a.size // self.elem_len,
+                    device=self._device)
+
+    def root(self) -> bytes:
+        """TreeHash of the current list of byte strings."""
+        out = ctypes.create_string_buffer(32)
+        _lib.invoke("mk_bytes_list_tree_root", self._handle, out, device=self._device)
+        return out.raw
+
+    def elems(self, first: int = 0, count: int = None) -> np.ndarray:
+        """Elements [first, first + count) read back as a (count, elem_len) uint8 array."""
+        if count is None:
+            count = len(self) - first
+        out = np.empty((max(count, 0), self.elem_len), dtype=np.uint8)
+        _lib.invoke("mk_bytes_list_tree_elems", self._handle, first, count, _ptr(out), device=self._device)
         return out
