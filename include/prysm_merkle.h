@@ -319,9 +319,39 @@ int mk_dev_ssz_merkle_hash_multi(mk_call* call, const void* const* d_shards, uin
  * structFields does, ssz_utils_cache.go:100).  Field hash = MK_FIELD_BYTES:
  * Keccak(le32(len) || bytes) (offset must be 4-byte aligned, record_len too);
  * MK_FIELD_RAW: raw little-endian scalar of len 1/2/4/8 (not hashed).
- * The struct root is Keccak(concat of field outputs). */
+ * The struct root is Keccak(concat of field outputs).
+ *
+ * The rest of makeStructHasher's type grammar (hash.go:141-178) keeps records
+ * flat, fixed-length and 4-byte aligned; there is no side heap:
+ * MK_FIELD_VARBYTES: a []byte of varying length in a slot of 4 + len bytes at
+ * a 4-byte aligned offset: le32(L), then L bytes, 0 <= L <= len (the capacity;
+ * the slot's other len - L bytes are ignored).  Field hash = Keccak(record[
+ * offset, offset + 4 + L)), which is hashedEncoding of the []byte
+ * (hash.go:100-107).  Device entry points cannot report a bad L: they clamp it
+ * to len and never read outside the slot.  The host-buffer and handle entry
+ * points (mk_ssz_struct_roots, mk_ssz_struct_list_root,
+ * mk_struct_list_tree_assign/update/append) check every record they are given
+ * and return MK_EINVAL, changing nothing, when some L > len.
+ * MK_FIELD_STRUCT: a nested struct, by value or by non-nil pointer
+ * (makePtrHasher only dereferences).  len = the number of mk_field entries
+ * that follow and belong to it, all its descendants flattened in pre-order
+ * (len == 0 is MK_EINVAL); offset must be 0, the children carry absolute
+ * record offsets.  Field hash = Keccak(concat of its direct children's
+ * outputs).  Nesting depth at most 4, the top-level struct counting as 1;
+ * at most 32 entries in all.
+ * Layouts with either kind hash in one launch, one record per thread, with
+ * each struct's message staged in LDS: the message lengths along any one
+ * root-to-leaf nesting path may sum to at most 320 bytes (each rounded up to
+ * 4), otherwise the layout is MK_EINVAL; their records must be 4-byte aligned.
+ *
+ * mk_ssz_struct_msg_len: the top-level struct's message length; for a layout
+ * with MK_FIELD_STRUCT entries the scratch bytes per record instead, the
+ * message lengths of the top-level struct and of every nested struct summed.
+ * 0 for a layout that is refused. */
 #define MK_FIELD_BYTES 1
 #define MK_FIELD_RAW 2
+#define MK_FIELD_VARBYTES 3
+#define MK_FIELD_STRUCT 4
 typedef struct mk_field {
     uint32_t kind;
     uint32_t offset;

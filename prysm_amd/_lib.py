@@ -160,10 +160,12 @@ _SIGS = {
 
 MK_FIELD_BYTES = 1
 MK_FIELD_RAW = 2
+MK_FIELD_VARBYTES = 3  # le32(L) || L bytes in a slot of 4 + len bytes
+MK_FIELD_STRUCT = 4    # a nested struct: len = the entries that follow and belong to it
 
 
 class Field(ctypes.Structure):
-    """mk_field: one field of a flat fixed-layout record."""
+    """mk_field: one field of a fixed-layout record."""
     _fields_ = [("kind", ctypes.c_uint32), ("offset", ctypes.c_uint32), ("len", ctypes.c_uint32)]
 
 

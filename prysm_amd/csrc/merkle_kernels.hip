@@ -1648,6 +1648,28 @@ __device__ __noinline__ void sponge_prefix4(const uint8_t* __restrict__ A, uint3
     digest(s, d0, d1);
 }
 
+// Keccak(le32(len) || A[0, len)) in one block, dword-granular: dword 0 =
+// le32(len), dwords 1.. = bytes (len % 4 == 0, len + 4 < 136, A 4-byte aligned)
+__device__ __forceinline__ void bytes_block_digest(const uint8_t* __restrict__ A, uint32_t len, uint4& d0,
+                                                   uint4& d1) {
+    const uint32_t* A32 = reinterpret_cast<const uint32_t*>(A);
+    const uint32_t nd = len / 4 + 1;  // message dwords
+    State s;
+    zero(s);
+#pragma unroll
+    for (int q = 0; q < 34; ++q) {
+        uint32_t v = q == 0 ? len : ((uint32_t)q < nd ? A32[q - 1] : 0u);
+        if ((uint32_t)q == nd) v ^= 1u;  // domain pad byte
+        if (q & 1)
+            s.hi[q / 2] ^= v;
+        else
+            s.lo[q / 2] ^= v;
+    }
+    s.hi[16] ^= 0x80000000u;
+    keccak_f_digest(s);
+    digest(s, d0, d1);
+}
+
 template <bool FAST>
 __global__ __launch_bounds__(256) void k_struct_fields(const uint8_t* __restrict__ rec, uint64_t n, StructSpec sp,
                                                        uint8_t* __restrict__ msg) {
@@ -1663,23 +1685,7 @@ __global__ __launch_bounds__(256) void k_struct_fields(const uint8_t* __restrict
     if (sp.kind[f] == 1) {  // MK_FIELD_BYTES
         uint4 d0, d1;
         if constexpr (FAST) {  // host-checked: every bytes field has len % 4 == 0, len + 4 < 136
-            // one block, dword-granular: dword 0 = le32(len), dwords 1.. = bytes
-            const uint32_t* A32 = reinterpret_cast<const uint32_t*>(r + off);
-            const uint32_t nd = len / 4 + 1;  // message dwords
-            State s;
-            zero(s);
-#pragma unroll
-            for (int q = 0; q < 34; ++q) {
-                uint32_t v = q == 0 ? len : ((uint32_t)q < nd ? A32[q - 1] : 0u);
-                if ((uint32_t)q == nd) v ^= 1u;  // domain pad byte
-                if (q & 1)
-                    s.hi[q / 2] ^= v;
-                else
-                    s.lo[q / 2] ^= v;
-            }
-            s.hi[16] ^= 0x80000000u;
-            keccak_f_digest(s);
-            digest(s, d0, d1);
+            bytes_block_digest(r + off, len, d0, d1);
         } else {
             sponge_prefix4(r + off, len, d0, d1);
         }
@@ -1811,6 +1817,176 @@ __global__ __launch_bounds__(kStructThreads) void k_struct_fused(const uint8_t* 
         roots[2 * i + 1] = d1;
     }
 }
+
+// Nested structs and variable-length byte fields (hash.go:141-178): one
+// record per thread, one launch.  The host flattens the layout into a program
+// (struct_spec.cpp): the fields in declaration order, a struct's close right
+// after its last descendant.  A struct's message is staged in the thread's
+// LDS column (dword-major as in k_struct_fused: column dword q of thread t at
+// col[q * NT + t], conflict-free) right behind its parent's; its close hashes
+// the region and stores the 32-B digest into the parent's message, after which
+// the next sibling struct reuses the region.  The column is therefore as long
+// as the largest sum of message lengths along one nesting path (ns.peak).
+//   MK_FIELD_BYTES:    one block (bytes_block_digest), else sponge_rec4
+//   MK_FIELD_VARBYTES: sponge_rec4 straight from the record over the stored
+//                      length clamped to the slot (per-lane data)
+//   MK_FIELD_RAW:      copied
+// Every op is uniform across the workgroup, so the only divergence is that
+// block loop of sponge_rec4.  No barrier: a thread only touches its own column.
+// Dynamic LDS: NT * ns.peak bytes.
+namespace {
+// nbytes (1..4) low bytes of v to column bytes [b, b + nbytes)
+template <uint32_t NT>
+__device__ __forceinline__ void col_put(uint32_t* col, uint32_t b, uint32_t v, uint32_t nbytes) {
+    const uint32_t q = b / 4, sh = 8 * (b % 4);
+    if (sh == 0 && nbytes == 4) {
+        col[q * NT] = v;
+        return;
+    }
+    const uint32_t mask = nbytes == 4 ? 0xFFFFFFFFu : (1u << (8 * nbytes)) - 1u;
+    v &= mask;
+    col[q * NT] = (col[q * NT] & ~(mask << sh)) | (v << sh);
+    if (sh + 8 * nbytes > 32) {
+        const uint32_t r = 32 - sh;  // bits that went into dword q
+        col[(q + 1) * NT] = (col[(q + 1) * NT] & ~(mask >> r)) | (v >> r);
+    }
+}
+
+// a 32-B digest to column bytes [b, b + 32): whole dwords when b % 4 == 0,
+// else the eight dwords shifted across nine (the first and the last merged
+// into what the column holds)
+template <uint32_t NT>
+__device__ __forceinline__ void col_put_digest(uint32_t* col, uint32_t b, const uint32_t (&dw)[8]) {
+    const uint32_t q = b / 4, sh = 8 * (b % 4);
+    if (sh == 0) {
+#pragma unroll
+        for (int w = 0; w < 8; ++w) col[(q + w) * NT] = dw[w];
+        return;
+    }
+    const uint32_t r = 32 - sh, lo = (1u << sh) - 1u;  // lo: the bytes of dword q below the digest
+    col[q * NT] = (col[q * NT] & lo) | (dw[0] << sh);
+#pragma unroll
+    for (int w = 1; w < 8; ++w) col[(q + w) * NT] = (dw[w - 1] >> r) | (dw[w] << sh);
+    col[(q + 8) * NT] = (col[(q + 8) * NT] & ~lo) | (dw[7] >> r);
+}
+
+// Keccak of column bytes [b, b + mlen), b % 4 == 0
+template <uint32_t NT>
+__device__ __forceinline__ void col_digest(const uint32_t* col, uint32_t b, uint32_t mlen, uint4& d0,
+                                           uint4& d1) {
+    const uint32_t q0 = b / 4, mw = mlen / 4, rem = mlen % 4, nb = mlen / 136 + 1;
+    State s;
+    zero(s);
+#pragma unroll 1
+    for (uint32_t blk = 0; blk < nb; ++blk) {
+#pragma unroll
+        for (int w = 0; w < 34; ++w) {
+            const uint32_t q = 34 * blk + w;
+            uint32_t v = q < mw ? col[(q0 + q) * NT] : 0u;
+            if (q == mw) {  // the last, partial dword and the domain pad byte
+                if (rem) v = col[(q0 + q) * NT] & ((1u << (8 * rem)) - 1u);
+                v ^= 1u << (8 * rem);
+            }
+            if (blk == nb - 1 && w == 33) v ^= 0x80000000u;
+            if (w & 1)
+                s.hi[w / 2] ^= v;
+            else
+                s.lo[w / 2] ^= v;
+        }
+        if (blk + 1 < nb)  // nb is uniform (one layout)
+            keccak_f(s);
+        else
+            keccak_f_digest(s);
+    }
+    digest(s, d0, d1);
+}
+}  // namespace
+
+// Keccak(le32(L) || A[0, L)) absorbed straight from the record, as
+// sponge_prefix4 does, for a length that differs between lanes: whole dwords
+// while they lie inside [0, L), the last partial dword from byte loads (no
+// read past A + L).  The block loop diverges: it runs to the wave's largest
+// block count while the lanes that are done sit masked off.
+__device__ __forceinline__ void sponge_rec4(const uint8_t* __restrict__ A, uint32_t L, uint4& d0, uint4& d1) {
+    const uint32_t* A32 = reinterpret_cast<const uint32_t*>(A);
+    const uint32_t len = L + 4, nb = len / 136 + 1;
+    uint32_t tail = 0;  // message dword len / 4: the L % 4 last bytes
+    for (uint32_t k = 0; k < (L & 3u); ++k) tail |= (uint32_t)A[(L & ~3u) + k] << (8 * k);
+    tail |= 1u << (8 * (L & 3u));  // domain pad byte
+    const uint32_t mw = len / 4;
+    State s;
+    zero(s);
+#pragma unroll 1
+    for (uint32_t b = 0; b < nb; ++b) {
+#pragma unroll
+        for (int w = 0; w < 34; ++w) {
+            const uint32_t q = 34 * b + w;  // message dword
+            uint32_t v = 0;
+            if (q == 0)
+                v = L;
+            else if (q < mw)
+                v = A32[q - 1];
+            else if (q == mw)
+                v = tail;
+            if (b == nb - 1 && w == 33) v ^= 0x80000000u;
+            if (w & 1)
+                s.hi[w / 2] ^= v;
+            else
+                s.lo[w / 2] ^= v;
+        }
+        keccak_f(s);
+    }
+    digest(s, d0, d1);
+}
+
+template <uint32_t NT>
+__global__ __launch_bounds__(NT) void k_struct_nested(const uint8_t* __restrict__ rec, uint64_t n, NestedSpec ns,
+                                                      uint4* __restrict__ roots) {
+    extern __shared__ uint32_t colbase[];
+    const uint32_t tid = threadIdx.x;
+    uint32_t* col = colbase + tid;
+    const uint64_t i = (uint64_t)blockIdx.x * NT + tid;
+    const bool live = i < n;
+    const uint8_t* r = rec + (live ? i : 0) * ns.rec_len;  // n >= 1: a spare lane re-hashes record 0
+#pragma unroll 1
+    for (uint32_t k = 0; k < ns.nops; ++k) {
+        const uint32_t kind = ns.op[k].kind, src = ns.op[k].src, len = ns.op[k].len, dst = ns.op[k].dst;
+        if (kind == 2) {  // MK_FIELD_RAW, len 1, 2, 4 or 8
+            if (((src | dst | len) & 3u) == 0) {
+                const uint32_t* A32 = reinterpret_cast<const uint32_t*>(r + src);
+                col[(dst / 4) * NT] = A32[0];
+                if (len == 8) col[(dst / 4 + 1) * NT] = A32[1];
+            } else {
+                for (uint32_t j = 0; j < len; ++j) col_put<NT>(col, dst + j, r[src + j], 1);
+            }
+            continue;
+        }
+        uint4 d0, d1;
+        if (kind == 1 && len % 4 == 0 && len + 4 < 136) {  // MK_FIELD_BYTES in one block
+            bytes_block_digest(r + src, len, d0, d1);
+        } else if (kind == 1) {  // MK_FIELD_BYTES of any other length
+            sponge_rec4(r + src, len, d0, d1);
+        } else if (kind == 3) {  // MK_FIELD_VARBYTES: le32(L) at src, then L <= len bytes
+            // (its own call: with the two kinds folded into one call -- pointer and length chosen by
+            // kind -- fixed bytes fields after the first digest of a record came out wrong on the device)
+            const uint32_t L = min(*reinterpret_cast<const uint32_t*>(r + src), len);
+            sponge_rec4(r + src + 4, L, d0, d1);
+        } else {  // kOpClose
+            col_digest<NT>(col, src, len, d0, d1);
+            if (k + 1 == ns.nops) {  // the top-level struct: the record's root
+                if (live) {
+                    roots[2 * i] = d0;
+                    roots[2 * i + 1] = d1;
+                }
+                break;
+            }
+        }
+        const uint32_t dw[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+        col_put_digest<NT>(col, dst, dw);
+    }
+}
+template __global__ void k_struct_nested<256>(const uint8_t*, uint64_t, NestedSpec, uint4*);
+template __global__ void k_struct_nested<128>(const uint8_t*, uint64_t, NestedSpec, uint4*);
 
 // Struct roots for the "bytes fields first, then 8-byte scalars" layout
 // (pb.Validator: 3 bytes fields + 6 uint64) with the message

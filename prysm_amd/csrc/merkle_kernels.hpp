@@ -4,21 +4,15 @@
 #include <stdint.h>
 
 #include "plan_types.hpp"
+#include "struct_spec.hpp"
 
 namespace mk {
 
-constexpr uint32_t kMaxStructFields = 32;
 #define MK_STRUCT_THREADS 256
 constexpr uint32_t kStructThreads = MK_STRUCT_THREADS;  // k_struct_fused: one record per thread
 constexpr uint32_t kStructFusedMaxMsg = 160;          // LDS: kStructThreads * msg_len bytes
 constexpr uint32_t kStructFusedMaxField = 64;         // bytes fields held in 16 registers
-struct StructSpec {                 // flat fixed-layout record (hash.go:141-159)
-    uint32_t kind[kMaxStructFields];   // 1 = bytes (hashed with le32 prefix), 2 = raw scalar
-    uint32_t off[kMaxStructFields];    // byte offset inside the record
-    uint32_t len[kMaxStructFields];    // field length in bytes
-    uint32_t out_off[kMaxStructFields];  // byte offset inside the struct message
-    uint32_t nfields, rec_len, msg_len;
-};
+// StructSpec, NestedSpec: struct_spec.hpp
 
 template <bool LEAF, bool FAST, int NI>
 __global__ void k_reduce(ReduceArgs a);
@@ -38,6 +32,10 @@ __global__ void k_elem_digests(const uint8_t* elems, uint64_t n, uint32_t elem_l
 template <bool FAST>
 __global__ void k_struct_fields(const uint8_t* rec, uint64_t n, StructSpec sp, uint8_t* msg);
 __global__ void k_struct_fused(const uint8_t* rec, uint64_t n, StructSpec sp, uint32_t vec16, uint4* roots);
+// nested structs and variable-length byte fields: one record per thread, one launch;
+// dynamic LDS NT * ns.peak bytes (NT = ns.threads)
+template <uint32_t NT>
+__global__ void k_struct_nested(const uint8_t* rec, uint64_t n, NestedSpec ns, uint4* roots);
 template <int NB, int NRAW>
 __global__ void k_struct_reg(const uint8_t* rec, uint64_t n, StructSpec sp, uint32_t vec16, uint4* roots);
 // validator layout (kValOff/kValLen in merkle_kernels.hip), any n (a partial last group);

@@ -159,10 +159,11 @@ uint32_t next_arrive_slots(uint32_t k);
 uint32_t top_arrive_slots(uint64_t parts);
 
 // ---- flat records (struct_api.cpp) ------------------------------------------------
-int struct_make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::StructSpec& sp);
-bool struct_fused_layout(const mk::StructSpec& sp);  // a layout k_struct_fused takes (4-B aligned records)
+int struct_make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::HostSpec& sp);
+// a layout whose roots launch needs no message buffer: what k_struct_fused or k_struct_nested takes (4-B aligned records)
+bool struct_fused_layout(const mk::HostSpec& sp);
 // roots of n records into d_roots (n x 32); d_msg: n x msg_len bytes (unused for a fused layout)
-int struct_launch_roots(const void* d_rec, uint64_t n, const mk::StructSpec& sp, void* d_msg, void* d_roots,
+int struct_launch_roots(const void* d_rec, uint64_t n, const mk::HostSpec& sp, void* d_msg, void* d_roots,
                         hipStream_t st);
 
 // ---- list tree over 32-B items (list_tree_api.cpp) -----------------------------------

@@ -9,39 +9,15 @@ using namespace mk::rt;
 namespace {
 
 // ---- struct hashing ---------------------------------------------------------------
-int make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::StructSpec& sp) {
-    if (!fields || nfields == 0 || nfields > mk::kMaxStructFields)
-        return fail(MK_EINVAL, "nfields %u out of range (1..%u)", nfields, mk::kMaxStructFields);
-    std::memset(&sp, 0, sizeof sp);
-    uint32_t out = 0;
-    for (uint32_t f = 0; f < nfields; ++f) {
-        const mk_field& fd = fields[f];
-        if (fd.kind == MK_FIELD_BYTES) {
-            if (fd.offset % 4) return fail(MK_EINVAL, "bytes field %u: offset not 4-byte aligned", f);
-        } else if (fd.kind == MK_FIELD_RAW) {
-            if (fd.len != 1 && fd.len != 2 && fd.len != 4 && fd.len != 8)
-                return fail(MK_EINVAL, "raw field %u: len %u not in {1,2,4,8}", f, fd.len);
-        } else {
-            return fail(MK_EINVAL, "field %u: unknown kind %u", f, fd.kind);
-        }
-        if (record_len && (uint64_t)fd.offset + fd.len > record_len)
-            return fail(MK_EINVAL, "field %u exceeds the record", f);
-        sp.kind[f] = fd.kind;
-        sp.off[f] = fd.offset;
-        sp.len[f] = fd.len;
-        sp.out_off[f] = out;
-        out += fd.kind == MK_FIELD_BYTES ? 32 : fd.len;
-    }
-    if (record_len % 4) return fail(MK_EINVAL, "record_len %u not a multiple of 4", record_len);
-    sp.nfields = nfields;
-    sp.rec_len = record_len;
-    sp.msg_len = out;
-    return MK_OK;
+// parsing and every check of the layout: struct_spec.cpp (no HIP, no device)
+int make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::HostSpec& sp) {
+    return mk::parse_struct_spec(fields, nfields, record_len, sp);
 }
 
 // k_struct_lock's compile-time layout: the SURVEY §8d ValidatorRecord
-// (3 bytes fields, 6 uint64, 160-B records)
-bool validator_layout(const mk::StructSpec& sp) {
+// (3 bytes fields, 6 uint64, 160-B records); never a layout with the nested kinds
+bool validator_layout(const mk::HostSpec& sp) {
+    if (sp.nested) return false;
     static const uint32_t off[9] = {0, 48, 80, 112, 120, 128, 136, 144, 152};
     static const uint32_t len[9] = {48, 32, 32, 8, 8, 8, 8, 8, 8};
     if (sp.nfields != 9 || sp.rec_len != 160 || sp.msg_len != 144) return false;
@@ -59,8 +35,10 @@ struct StructForm {
     bool fused, vec16, layout, split;
     uint32_t nb, nraw;
 };
-StructForm struct_form(const void* d_rec, uint64_t n, const mk::StructSpec& sp) {
+StructForm struct_form(const void* d_rec, uint64_t n, const mk::HostSpec& sp) {
     StructForm f{};
+    f.split = n <= mk::kStructSplitMaxN;
+    if (sp.nested) return f;  // MK_FIELD_VARBYTES / _STRUCT: k_struct_nested alone takes them
     // fused path: dword-granular single-block fields, dword-aligned message
     f.fused = sp.msg_len % 4 == 0 && sp.msg_len <= mk::kStructFusedMaxMsg && ((uintptr_t)d_rec % 4) == 0;
     f.vec16 = ((uintptr_t)d_rec % 16) == 0 && sp.rec_len % 16 == 0;
@@ -85,9 +63,23 @@ StructForm struct_form(const void* d_rec, uint64_t n, const mk::StructSpec& sp) 
 }
 
 // roots of n records into d_roots (n x 32); d_msg holds n x msg_len bytes
-int launch_struct_roots(const void* d_rec, uint64_t n, const mk::StructSpec& sp, void* d_msg, void* d_roots,
+int launch_struct_roots(const void* d_rec, uint64_t n, const mk::HostSpec& sp, void* d_msg, void* d_roots,
                         hipStream_t st) {
     if (n == 0) return MK_OK;
+    if (sp.nested) {  // nested structs, variable-length byte fields: one launch, messages in LDS
+        if ((uintptr_t)d_rec % 4) return fail(MK_EINVAL, "records of a nested layout must be 4-byte aligned");
+        if (sp.rec_len == 0) return fail(MK_EINVAL, "record_len == 0");
+        const mk::NestedSpec& ns = sp.prog;
+        if (ns.threads == mk::kNestedThreadsMax)
+            hipLaunchKernelGGL((mk::k_struct_nested<mk::kNestedThreadsMax>), dim3(ceil_div(n, ns.threads)),
+                               dim3(ns.threads), ns.threads * ns.peak, st, (const uint8_t*)d_rec, n, ns,
+                               (uint4*)d_roots);
+        else
+            hipLaunchKernelGGL((mk::k_struct_nested<mk::kNestedThreadsMin>), dim3(ceil_div(n, ns.threads)),
+                               dim3(ns.threads), ns.threads * ns.peak, st, (const uint8_t*)d_rec, n, ns,
+                               (uint4*)d_roots);
+        return launched();
+    }
     const StructForm sf = struct_form(d_rec, n, sp);
     const bool fused = sf.fused, vec16 = sf.vec16, layout = sf.layout, split = sf.split;
     const uint32_t nb = sf.nb, nraw = sf.nraw;
@@ -160,7 +152,7 @@ constexpr uint64_t kH2dMinChunk = MK_H2D_MIN_CHUNK;
 // finish from the windows (dev_finish_nodes: the same odd rule at every
 // level, hash.go:225-237).  false: not this layout / size (caller takes the
 // two-launch path).
-bool struct_win_ok(const void* d_rec, uint64_t n, const mk::StructSpec& sp) {
+bool struct_win_ok(const void* d_rec, uint64_t n, const mk::HostSpec& sp) {
     if (n < (1u << 18)) return false;
     if (((uintptr_t)d_rec % 16) != 0 || sp.rec_len % 16 != 0 || !validator_layout(sp)) return false;
     for (uint32_t f = 0; f < sp.nfields; ++f)
@@ -203,11 +195,11 @@ int dev_struct_list_root_win(const void* d_rec, uint64_t n, void* d_roots, void*
 // scalars: C1) in ONE launch, k_struct_list_fused<3, 6>: the k_struct_split
 // records, the latency list tree's windows and levels, and the fused top's
 // groups and mix-in, where they were three launches (round 6)
-bool struct_list_fused_ok(const void* d_rec, uint64_t n, const mk::StructSpec& sp) {
+bool struct_list_fused_ok(const void* d_rec, uint64_t n, const mk::HostSpec& sp) {
     const StructForm f = struct_form(d_rec, n, sp);
     return n && f.layout && f.split && f.nb == 3 && f.nraw == 6 && list_tree_ok(n, 32);
 }
-int launch_struct_list_fused(const void* d_rec, uint64_t n, const mk::StructSpec& sp, uint8_t* d_roots,
+int launch_struct_list_fused(const void* d_rec, uint64_t n, const mk::HostSpec& sp, uint8_t* d_roots,
                              uint8_t* d_sub, void* d_out32, hipStream_t st) {
     if (inject_ehip()) return fail(MK_EHIP, "hipLaunchKernelGGL: injected failure (MK_INJECT_EHIP)");
     const StructForm f = struct_form(d_rec, n, sp);
@@ -226,7 +218,7 @@ int launch_struct_list_fused(const void* d_rec, uint64_t n, const mk::StructSpec
     return launched();
 }
 
-uint64_t struct_list_ws(uint64_t n, const mk::StructSpec& sp) {
+uint64_t struct_list_ws(uint64_t n, const mk::HostSpec& sp) {
     Plan p;
     uint64_t mws = 256;
     if (mk::make_plan(n, 32, false, 0, false, true, p) == MK_OK && !p.small) mws = mk::plan_ws_bytes(p);
@@ -259,7 +251,7 @@ struct PipeTree {
 };
 PipeTree pipe_reg(uint64_t n) { return {512, 10, ceil_div(n, 8)}; }
 PipeTree pipe_val(uint64_t nvalues, uint32_t value_len) { return {128, 4, ceil_div(nvalues * value_len, 256)}; }
-bool struct_pipe_ok(const void* d_rec, uint64_t n, const mk::StructSpec& sp, hipStream_t st) {
+bool struct_pipe_ok(const void* d_rec, uint64_t n, const mk::HostSpec& sp, hipStream_t st) {
     return struct_win_ok(d_rec, n, sp) && struct_gpw(n, st) == 4 && pipe_reg(n).nfull() >= 1;
 }
 
@@ -276,9 +268,10 @@ uint64_t pipe_top_ws(const PipeTree& t) {
 
 int host_struct_roots(const uint8_t* records, uint64_t n, uint32_t record_len, const mk_field* fields,
                       uint32_t nfields, uint8_t* roots) {
-    mk::StructSpec sp;
+    mk::HostSpec sp;
     TRY(make_spec(fields, nfields, record_len, sp));
     if (n && (!records || !roots)) return fail(MK_EINVAL, "null pointer");
+    TRY(mk::check_var_lengths(sp, records, n));
     TRY(bind_call());
     if (n == 0) return MK_OK;
     DevCtx* c = ctx();
@@ -296,9 +289,10 @@ int host_struct_roots(const uint8_t* records, uint64_t n, uint32_t record_len, c
 
 int host_struct_list_root(const uint8_t* records, uint64_t n, uint32_t record_len, const mk_field* fields,
                           uint32_t nfields, uint8_t* out) {
-    mk::StructSpec sp;
+    mk::HostSpec sp;
     TRY(make_spec(fields, nfields, record_len, sp));
     if (!out || (n && !records)) return fail(MK_EINVAL, "null pointer");
+    TRY(mk::check_var_lengths(sp, records, n));
     TRY(bind_call());
     DevCtx* c = ctx();
     std::lock_guard<std::mutex> lk(c->mu);
@@ -346,11 +340,11 @@ int host_struct_list_root(const uint8_t* records, uint64_t n, uint32_t record_le
 
 // what the registry tree (struct_tree_api.cpp) takes from here
 namespace mk::rt {
-int struct_make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::StructSpec& sp) {
+int struct_make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::HostSpec& sp) {
     return make_spec(fields, nfields, record_len, sp);
 }
-bool struct_fused_layout(const mk::StructSpec& sp) { return struct_form(nullptr, 0, sp).fused; }
-int struct_launch_roots(const void* d_rec, uint64_t n, const mk::StructSpec& sp, void* d_msg, void* d_roots,
+bool struct_fused_layout(const mk::HostSpec& sp) { return sp.nested || struct_form(nullptr, 0, sp).fused; }
+int struct_launch_roots(const void* d_rec, uint64_t n, const mk::HostSpec& sp, void* d_msg, void* d_roots,
                         hipStream_t st) {
     return launch_struct_roots(d_rec, n, sp, d_msg, d_roots, st);
 }
@@ -361,14 +355,14 @@ extern "C" {
 // ---- struct hashing ---------------------------------------------------------------
 uint64_t mk_ssz_struct_msg_len(const mk_field* fields, uint32_t nfields) {
     Scope S(nullptr, false);
-    mk::StructSpec sp;
+    mk::HostSpec sp;
     if (make_spec(fields, nfields, 0, sp) != MK_OK) return 0;
     return sp.msg_len;
 }
 
 uint64_t mk_ssz_struct_list_workspace_bytes(uint64_t n, const mk_field* fields, uint32_t nfields) {
     Scope S(nullptr, false);
-    mk::StructSpec sp;
+    mk::HostSpec sp;
     if (make_spec(fields, nfields, 0, sp) != MK_OK) return 0;
     return struct_list_ws(n, sp);
 }
@@ -377,7 +371,7 @@ int mk_dev_ssz_struct_list_root(mk_call* call, const void* d_records, uint64_t n
                                 const mk_field* fields, uint32_t nfields, void* d_out32, void* d_ws,
                                 uint64_t ws_bytes, void* stream) {
     return dev_entry(call, stream, [&]() -> int {
-        mk::StructSpec sp;
+        mk::HostSpec sp;
         TRY(make_spec(fields, nfields, record_len, sp));
         if (ws_bytes < struct_list_ws(n, sp)) return fail(MK_ENOMEM, "workspace too small");
         if (n && !d_records) return fail(MK_EINVAL, "null pointer");
@@ -399,7 +393,7 @@ int mk_dev_ssz_struct_list_root(mk_call* call, const void* d_records, uint64_t n
 int mk_ssz_struct_list_level1_ok(const void* d_records, uint64_t n, uint32_t record_len, const mk_field* fields,
                                  uint32_t nfields) {
     Scope S(nullptr, false);
-    mk::StructSpec sp;
+    mk::HostSpec sp;
     if (make_spec(fields, nfields, record_len, sp) != MK_OK) return 0;
     return struct_win_ok(d_records, n, sp) ? 1 : 0;
 }
@@ -409,7 +403,7 @@ int mk_dev_ssz_struct_list_level1(mk_call* call, const void* d_records, uint64_t
                                   const void* d_values, uint64_t nvalues, uint32_t value_len, void* d_value_nodes,
                                   void* stream) {
     return dev_entry(call, stream, [&]() -> int {
-        mk::StructSpec sp;
+        mk::HostSpec sp;
         TRY(make_spec(fields, nfields, record_len, sp));
         if (!d_records || !d_roots || !d_nodes) return fail(MK_EINVAL, "null pointer");
         if (!struct_win_ok(d_records, n, sp))
@@ -429,7 +423,7 @@ int mk_dev_ssz_struct_list_level1(mk_call* call, const void* d_records, uint64_t
 int mk_ssz_struct_pipe_ok(const void* d_records, uint64_t n, uint32_t record_len, const mk_field* fields,
                           uint32_t nfields, void* stream) {
     Scope S(nullptr);
-    mk::StructSpec sp;
+    mk::HostSpec sp;
     if (make_spec(fields, nfields, record_len, sp) != MK_OK || bind_stream((hipStream_t)stream)) return S.done(0);
     return S.done(struct_pipe_ok(d_records, n, sp, (hipStream_t)stream) ? 1 : 0);
 }
@@ -451,7 +445,7 @@ int mk_dev_ssz_struct_list_level1_pipe(mk_call* call, const void* d_records, uin
                                        void* d_value_nodes, const void* d_prev_nodes, void* d_prev_levels,
                                        const void* d_prev_value_nodes, void* d_prev_value_levels, void* stream) {
     return dev_entry(call, stream, [&]() -> int {
-        mk::StructSpec sp;
+        mk::HostSpec sp;
         TRY(make_spec(fields, nfields, record_len, sp));
         if (!d_records || !d_roots || !d_nodes || (d_prev_nodes && !d_prev_levels) ||
             (d_prev_value_nodes && !d_prev_value_levels))
@@ -526,7 +520,7 @@ int mk_dev_ssz_struct_roots(mk_call* call, const void* d_records, uint64_t n, ui
                             const mk_field* fields, uint32_t nfields, void* d_roots, void* d_ws, uint64_t ws_bytes,
                             void* stream) {
     return dev_entry(call, stream, [&]() -> int {
-        mk::StructSpec sp;
+        mk::HostSpec sp;
         TRY(make_spec(fields, nfields, record_len, sp));
         if (n && (!d_records || !d_roots)) return fail(MK_EINVAL, "null pointer");
         if (ws_bytes < n * (uint64_t)sp.msg_len) return fail(MK_ENOMEM, "workspace too small");

@@ -11,8 +11,8 @@ using namespace mk::rt;
 // ---- registry tree handle ----------------------------------------------------------------
 namespace {
 struct Layout {
-    mk::StructSpec sp;
-    bool fused;    // the struct-roots launch needs no message buffer (what k_struct_fused takes)
+    mk::HostSpec sp;
+    bool fused;    // the struct-roots launch needs no message buffer (k_struct_fused, k_struct_nested)
     uint32_t ext;  // bytes of a record the fields reach, rounded up to 4 (<= rec_len)
 };
 }  // namespace
@@ -42,7 +42,11 @@ int st_layout(const mk_field* fields, uint32_t nfields, uint32_t record_len, Lay
     TRY(struct_make_spec(fields, nfields, record_len, L.sp));
     L.fused = struct_fused_layout(L.sp);
     uint32_t ext = 4;
-    for (uint32_t f = 0; f < L.sp.nfields; ++f) ext = std::max(ext, (L.sp.off[f] + L.sp.len[f] + 3) & ~3u);
+    for (uint32_t f = 0; f < L.sp.nfields; ++f) {
+        if (L.sp.kind[f] == MK_FIELD_STRUCT) continue;  // no bytes of its own
+        const uint32_t slot = L.sp.kind[f] == MK_FIELD_VARBYTES ? 4 + L.sp.len[f] : L.sp.len[f];
+        ext = std::max(ext, (L.sp.off[f] + slot + 3) & ~3u);
+    }
     L.ext = ext;
     return MK_OK;
 }
@@ -120,14 +124,14 @@ int launch_composed(const Layout& L, const void* d_records, uint64_t n_old, uint
     const uint64_t n_app = n_new - n_old, T = k_idx + n_app;
     const UpdateWs w = update_ws(L, T);
     uint8_t* ws = (uint8_t*)d_ws;
-    mk::StructSpec sp = L.sp;
+    mk::HostSpec sp = L.sp;
     const void* src = d_values;  // holds them in work-item order already
     if (!src) {
         hipLaunchKernelGGL(mk::k_struct_tree_gather, dim3(ceil_div(T * (L.ext / 4), 256)), dim3(256), 0, st,
                            (const uint8_t*)d_records, d_idx, k_idx, n_old, n_app, L.sp.rec_len, L.ext, ws + w.gath);
         HIPCHK(hipGetLastError());
         src = ws + w.gath;
-        sp.rec_len = L.ext;
+        sp.rec_len = sp.prog.rec_len = L.ext;
     }
     TRY(struct_launch_roots(src, T, sp, ws + w.msg, ws + w.roots, st));
     TRY(list_tree_scatter(d_roots, d_idx, k_idx, n_old, n_app, 32, ws + w.roots, st));
@@ -172,6 +176,7 @@ bool rebuild_pays(uint64_t dirty, uint64_t count) { return dirty && count / kReb
 int tree_assign(mk_struct_list_tree* t, const uint8_t* records, uint64_t n) {
     if (!t || (n && !records)) return fail(MK_EINVAL, "null pointer");
     std::lock_guard<std::mutex> tl(t->mu);
+    TRY(mk::check_var_lengths(t->L.sp, records, n));
     TRY(bind_dev(t->dev));
     hipStream_t st = ctx()->stream;
     if (n > t->cap) TRY(tree_alloc(t, n));
@@ -190,6 +195,7 @@ int tree_update(mk_struct_list_tree* t, const uint64_t* idx, const uint8_t* reco
             return fail(MK_EINVAL, "index %llu beyond %llu records", (unsigned long long)idx[i],
                         (unsigned long long)t->count);
     if (k == 0) return MK_OK;
+    TRY(mk::check_var_lengths(t->L.sp, records, k));
     // list[idx[j]] = records[j] in sequence: ascending indices, the last value of a repeated one
     std::vector<uint64_t> order(k);
     for (uint64_t i = 0; i < k; ++i) order[i] = i;
@@ -230,6 +236,7 @@ int tree_append(mk_struct_list_tree* t, const uint8_t* records, uint64_t k) {
     if (k == 0) return MK_OK;
     if (k >= kMaxWork || t->count + k < k)
         return fail(MK_EINVAL, "%llu records in one append", (unsigned long long)k);
+    TRY(mk::check_var_lengths(t->L.sp, records, k));
     TRY(bind_dev(t->dev));
     hipStream_t st = ctx()->stream;
     const uint32_t R = t->L.sp.rec_len;

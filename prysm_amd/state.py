@@ -10,18 +10,18 @@ declaration order (proto/beacon/p2p/v1/types.pb.go:50-79, the XXX_ fields
 skipped as structFields does, ssz_utils_cache.go:100), computed with a fixed
 number of batched library calls instead of one Keccak per field element:
 
-  1. every 32-B bytes field of the state (randao mixes, block / batched /
-     index roots, crosslink roots, attestation-data roots, eth1 hashes,
-     seeds): hashedEncoding K(le32(32) || b), one 36-B batch; the variable
-     length bitfields one var-length batch;
+  1. every 32-B bytes field that is a list element or a state field (randao
+     mixes, block / batched / index roots, seeds): hashedEncoding
+     K(le32(32) || b), one 36-B batch;
   2. the validator registry: typed struct roots + merkleHash
      (mk_ssz_struct_list_root, the Hashable fast path of registry.py);
-  3. struct messages of the small structs (CrosslinkRecord, AttestationData,
-     Eth1Data), one var-length batch; then PendingAttestationRecord and
-     Eth1DataVote (their messages contain step-3 roots), one more batch;
-  4. every list of the state (balances, the 8192-entry root arrays, penalized
-     balances, crosslinks, attestations, eth1 votes) in ONE segmented
-     merkleHash call (mk_ssz_merkle_many);
+  3. the three struct lists (CrosslinkRecord, PendingAttestationRecord with
+     its nested AttestationData and variable-length bitfields, Eth1DataVote
+     with its nested Eth1Data) packed into flat record arrays with numpy and
+     rooted by one mk_ssz_struct_list_root each (MK_FIELD_STRUCT,
+     MK_FIELD_VARBYTES); LatestEth1Data as a one-record struct root;
+  4. every other list of the state (balances, the 8192-entry root arrays,
+     penalized balances) in ONE segmented merkleHash call (mk_ssz_merkle_many);
   5. the state struct: K(concatenation of the 25 field outputs).
 
 SSZ legality: ``Validator.StatusFlags`` is an int32 enum,
@@ -39,9 +39,10 @@ from typing import List
 
 import numpy as np
 
+from . import _lib
 from . import registry as R
 from . import ssz as S
-from .hashutil import hash_batch, hash_batch_var
+from .hashutil import _ptr, hash_batch, hash_batch_var
 
 # shared/params/config.go:96-105
 SHARD_COUNT = 1024
@@ -120,6 +121,111 @@ class Attestations:
         return len(self.slot)
 
 
+# ---- typed layouts of the state's struct lists (mk_field: (kind, offset, len)) ----------------
+_BY, _RAW, _VAR, _STRUCT = _lib.MK_FIELD_BYTES, _lib.MK_FIELD_RAW, _lib.MK_FIELD_VARBYTES, _lib.MK_FIELD_STRUCT
+
+CROSSLINK_FIELDS = [(_RAW, 0, 8), (_BY, 8, 32)]                    # 40-B records
+ETH1_DATA_FIELDS = [(_BY, 0, 32), (_BY, 32, 32)]                   # 64-B records
+ETH1_VOTE_FIELDS = [(_STRUCT, 0, 2)] + ETH1_DATA_FIELDS + [(_RAW, 64, 8)]  # 72-B records
+# AttestationData at record offset 0 (192 B)
+_ATT_DATA_FIELDS = [(_RAW, 0, 8), (_RAW, 8, 8), (_BY, 16, 32), (_BY, 48, 32), (_BY, 80, 32), (_BY, 112, 32),
+                    (_RAW, 144, 8), (_BY, 152, 32), (_RAW, 184, 8)]
+
+
+def pending_attestation_fields(bitfield_cap: int):
+    """The PendingAttestationRecord layout for bitfield slots of
+    ``bitfield_cap`` bytes (a multiple of 4): AttestationData, the two
+    bitfield slots (le32 length + capacity), SlotIncluded; 13 entries."""
+    if bitfield_cap % 4:
+        raise ValueError("bitfield capacity must be a multiple of 4")
+    slot = 4 + bitfield_cap
+    return ([(_STRUCT, 0, len(_ATT_DATA_FIELDS))] + _ATT_DATA_FIELDS +
+            [(_VAR, 192, bitfield_cap), (_VAR, 192 + slot, bitfield_cap), (_RAW, 192 + 2 * slot, 8)])
+
+
+def pending_attestation_record_len(bitfield_cap: int) -> int:
+    return 192 + 2 * (4 + bitfield_cap) + 8
+
+
+PENDING_ATTESTATION_FIELDS = pending_attestation_fields(48)  # synthetic_state's bitfields: 16..47 bytes
+
+
+def _le64(x) -> np.ndarray:
+    return np.ascontiguousarray(x, dtype="<u8").reshape(-1, 1).view(np.uint8)
+
+
+def _put_bitfields(rec: np.ndarray, off: int, cap: int, fields: List[bytes]) -> None:
+    """le32(len) || bytes into the slot at column ``off`` of every record."""
+    lens = np.fromiter((len(x) for x in fields), dtype=np.int64, count=len(fields))
+    if len(fields) and lens.max() > cap:
+        raise ValueError(f"bitfield of {int(lens.max())} bytes in a {cap}-byte slot")
+    rec[:, off:off + 4] = lens.astype("<u4").reshape(-1, 1).view(np.uint8)
+    flat = np.frombuffer(b"".join(fields), dtype=np.uint8)
+    row = np.repeat(np.arange(len(fields)), lens)
+    col = np.arange(flat.size) - np.repeat(np.cumsum(lens) - lens, lens)
+    rec[row, off + 4 + col] = flat
+
+
+def pack_attestations(att: "Attestations", bitfield_cap: int = None):
+    """[]*PendingAttestationRecord as flat records: (records (a, record_len)
+    uint8, fields).  The bitfield slots are sized to the longest bitfield
+    rounded up to 4 (at least 4) unless ``bitfield_cap`` is given."""
+    a = len(att)
+    if bitfield_cap is None:
+        longest = max([len(x) for x in att.aggregation_bitfield] + [len(x) for x in att.custody_bitfield] + [1])
+        bitfield_cap = (longest + 3) & ~3
+    slot = 4 + bitfield_cap
+    rec = np.zeros((a, pending_attestation_record_len(bitfield_cap)), dtype=np.uint8)
+    rec[:, 0:8] = _le64(att.slot)
+    rec[:, 8:16] = _le64(att.shard)
+    rec[:, 16:144] = np.asarray(att.roots, dtype=np.uint8).reshape(a, 128)
+    rec[:, 144:152] = _le64(att.justified_epoch)
+    rec[:, 152:184] = np.asarray(att.justified_root, dtype=np.uint8).reshape(a, 32)
+    rec[:, 184:192] = _le64(att.justified_slot)
+    _put_bitfields(rec, 192, bitfield_cap, att.aggregation_bitfield)
+    _put_bitfields(rec, 192 + slot, bitfield_cap, att.custody_bitfield)
+    rec[:, 192 + 2 * slot:] = _le64(att.slot_included)
+    return rec, pending_attestation_fields(bitfield_cap)
+
+
+def pack_eth1_votes(votes: np.ndarray, counts: np.ndarray) -> np.ndarray:
+    """[]*Eth1DataVote as (v, 72) uint8 records of ETH1_VOTE_FIELDS."""
+    v = len(votes)
+    rec = np.empty((v, 72), dtype=np.uint8)
+    rec[:, :64] = np.asarray(votes, dtype=np.uint8).reshape(v, 64)
+    rec[:, 64:] = _le64(counts)
+    return rec
+
+
+def pack_crosslinks(epochs: np.ndarray, roots: np.ndarray) -> np.ndarray:
+    """[]*CrosslinkRecord as (s, 40) uint8 records of CROSSLINK_FIELDS."""
+    s = len(epochs)
+    rec = np.empty((s, 40), dtype=np.uint8)
+    rec[:, :8] = _le64(epochs)
+    rec[:, 8:] = np.asarray(roots, dtype=np.uint8).reshape(s, 32)
+    return rec
+
+
+def struct_list_root_packed(rec: np.ndarray, fields) -> bytes:
+    """TreeHash of a list of packed records ((n, record_len) uint8)."""
+    import ctypes
+
+    rec = np.ascontiguousarray(rec, dtype=np.uint8)
+    out = ctypes.create_string_buffer(32)
+    _lib.invoke("mk_ssz_struct_list_root", _ptr(rec) if rec.size else None, rec.shape[0], rec.shape[1],
+                R._fields(fields), len(fields), out)
+    return out.raw
+
+
+def struct_roots_packed(rec: np.ndarray, fields) -> np.ndarray:
+    """Struct root of every packed record -> (n, 32) uint8."""
+    rec = np.ascontiguousarray(rec, dtype=np.uint8)
+    out = np.empty((rec.shape[0], 32), dtype=np.uint8)
+    _lib.invoke("mk_ssz_struct_roots", _ptr(rec) if rec.size else None, rec.shape[0], rec.shape[1],
+                R._fields(fields), len(fields), _ptr(out))
+    return out
+
+
 @dataclass
 class BeaconState:
     """A synthetic, SSZ-legal pb.BeaconState with its lists as flat arrays."""
@@ -142,48 +248,33 @@ class BeaconState:
 
     # ---------------------------------------------------------------- the engine path
     def tree_hash_ssz(self) -> bytes:
-        """ssz.TreeHash(state): 7 library calls, no per-element Python work."""
-        att = self.attestations
-        a, v = len(att), len(self.eth1_votes)
-        # 1. hashedEncoding of every 32-B bytes field, one fixed-length batch
-        b32 = np.concatenate([self.randao_mixes, self.seeds, self.crosslink_roots, self.latest_block_roots,
-                              self.batched_block_roots, self.index_roots, att.roots.reshape(-1, 32),
-                              att.justified_root, self.eth1_data, self.eth1_votes.reshape(-1, 32)])
+        """ssz.TreeHash(state): a fixed number of library calls, no per-element Python work."""
+        # 1. hashedEncoding of the 32-B list elements and state fields, one fixed-length batch
+        b32 = np.concatenate([self.randao_mixes, self.seeds, self.latest_block_roots, self.batched_block_roots,
+                              self.index_roots])
         msgs = np.empty((len(b32), 36), dtype=np.uint8)
         msgs[:, :4] = np.frombuffer(_st.pack("<I", 32), dtype=np.uint8)
         msgs[:, 4:] = b32
         h = hash_batch(msgs, 36)
-        cut = np.cumsum([0, len(self.randao_mixes), 2, len(self.crosslink_roots), len(self.latest_block_roots),
-                         len(self.batched_block_roots), len(self.index_roots), 4 * a, a, 2, 2 * v])
-        h_randao, h_seeds, h_cross, h_block, h_batched, h_index, h_att4, h_just, h_eth1, h_votes = (
-            h[cut[i]:cut[i + 1]] for i in range(10))
-        h_att4 = h_att4.reshape(a, 4 * 32)
-        bits = hash_batch_var([_st.pack("<I", len(x)) + x for x in att.aggregation_bitfield + att.custody_bitfield])
+        cut = np.cumsum([0, len(self.randao_mixes), 2, len(self.latest_block_roots), len(self.batched_block_roots),
+                         len(self.index_roots)])
+        h_randao, h_seeds, h_block, h_batched, h_index = (h[cut[i]:cut[i + 1]] for i in range(5))
         # 2. the registry (typed Hashable path: struct kernel + merkleHash)
         reg_root = self.registry.tree_hash_ssz()
-        # 3. small structs: CrosslinkRecord, AttestationData, Eth1Data (latest + per vote)
-        le = lambda x: np.ascontiguousarray(x, dtype="<u8").reshape(-1, 1).view(np.uint8)  # noqa: E731
-        cross_msg = np.concatenate([le(self.crosslink_epochs), h_cross], axis=1)
-        att_msg = np.concatenate([le(att.slot), le(att.shard), h_att4, le(att.justified_epoch), h_just,
-                                  le(att.justified_slot)], axis=1)
-        eth1_msg = np.concatenate([h_eth1.reshape(1, 64), h_votes.reshape(v, 64)])
-        r3 = hash_batch_var([bytes(r) for r in cross_msg] + [bytes(r) for r in att_msg] + [bytes(r) for r in eth1_msg])
-        cross_roots = b"".join(r3[:len(cross_msg)])
-        att_data = r3[len(cross_msg):len(cross_msg) + a]
-        eth1_root, vote_eth1 = r3[len(cross_msg) + a], r3[len(cross_msg) + a + 1:]
-        # PendingAttestationRecord / Eth1DataVote messages hold step-3 roots
-        rec_msgs = [att_data[i] + bits[i] + bits[a + i] + _st.pack("<Q", int(att.slot_included[i]))
-                    for i in range(a)]
-        vote_msgs = [vote_eth1[i] + _st.pack("<Q", int(self.eth1_vote_counts[i])) for i in range(v)]
-        r4 = hash_batch_var(rec_msgs + vote_msgs)
-        att_roots, vote_roots = b"".join(r4[:a]), b"".join(r4[a:])
-        # 4. every list of the state in one segmented merkleHash call
+        # 3. the struct lists from packed records: nested structs and bitfields hash on the device
+        cross_root = struct_list_root_packed(pack_crosslinks(self.crosslink_epochs, self.crosslink_roots),
+                                             CROSSLINK_FIELDS)
+        att_rec, att_fields = pack_attestations(self.attestations)
+        att_root = struct_list_root_packed(att_rec, att_fields)
+        votes_root = struct_list_root_packed(pack_eth1_votes(self.eth1_votes, self.eth1_vote_counts),
+                                             ETH1_VOTE_FIELDS)
+        eth1_root = bytes(struct_roots_packed(np.ascontiguousarray(self.eth1_data, dtype=np.uint8).reshape(1, 64),
+                                              ETH1_DATA_FIELDS)[0])
+        # 4. every other list of the state in one segmented merkleHash call
         lists = [(self.balances.astype("<u8").view(np.uint8), len(self.balances), 8),
-                 (h_randao, len(h_randao), 32), (np.frombuffer(cross_roots, np.uint8), len(cross_msg), 32),
-                 (h_block, len(h_block), 32), (h_batched, len(h_batched), 32),
+                 (h_randao, len(h_randao), 32), (h_block, len(h_block), 32), (h_batched, len(h_batched), 32),
                  (self.penalized_balances.astype("<u8").view(np.uint8), len(self.penalized_balances), 8),
-                 (np.frombuffer(att_roots, np.uint8), a, 32), (h_index, len(h_index), 32),
-                 (np.frombuffer(vote_roots, np.uint8), v, 32)]
+                 (h_index, len(h_index), 32)]
         buf, offs, pos = [], [], 0
         for arr, _, _ in lists:
             pad = (-pos) % 16
@@ -194,8 +285,7 @@ class BeaconState:
             buf.append(flat)
             pos += flat.size
         roots = _merkle_many_mixed(np.concatenate(buf), offs, [x[1] for x in lists], [x[2] for x in lists])
-        (bal_root, randao_root, cross_root, block_root, batched_root, pen_root, att_root, index_root,
-         votes_root) = roots
+        bal_root, randao_root, block_root, batched_root, pen_root, index_root = roots
         # 5. the state struct: field outputs in declaration order
         sc = self.scalars
         u = lambda name: _st.pack("<Q", int(sc[name]))  # noqa: E731
