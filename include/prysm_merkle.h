@@ -561,6 +561,68 @@ int mk_bytes_list_tree_root(mk_call* call, mk_bytes_list_tree* t, uint8_t root[3
 /* Elements [first, first + cnt), cnt x elem_len bytes. */
 int mk_bytes_list_tree_elems(mk_call* call, mk_bytes_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
 
+/* ---- several device-resident trees, and the struct that holds them, in one call --- */
+/* mk_dev_ssz_trees_update runs the update of up to MK_TREES_MAX resident trees
+ * of any of the three kinds above in one call: every tree's stage 0 (its
+ * values scattered in, its struct roots or element digests), then ONE launch
+ * in which all the trees climb side by side, about as long as the deepest of
+ * them.  For every tree the result in d_items, d_level0, d_levels and d_root32
+ * is byte for byte what that kind's own mk_dev_ssz_*_tree_update leaves with
+ * the same arguments (an index >= n_old ignored, appends, nothing changed,
+ * lists of at most one chunk), and each kind's own argument rules hold.
+ * `trees` is host memory, read only during the call.
+ * Container: a struct whose list fields are these trees (makeStructHasher,
+ * hash.go:141-159).  d_container (4-B aligned, container_len = 1 ..
+ * MK_CONTAINER_MAX bytes) is the struct's hash message with every other
+ * field's output already written by the caller on this stream; tree i's root
+ * is also stored at container_off[i] (4-B aligned, the 32-B ranges disjoint
+ * and inside the message; MK_NO_CONTAINER: the tree is no field of it), and
+ * the last tree to finish hashes the message into d_container_root32 (4-B
+ * aligned) in the same launch.  container_len == 0: no container, d_container
+ * and d_container_root32 may be NULL and are not touched.
+ * Workspace (16-B aligned) from mk_ssz_trees_update_workspace_bytes (the sum of
+ * the per-kind update workspaces plus the container's counter; 0 for a tree
+ * list the call would refuse): the call zeroes its arrival words and owns it
+ * until it has run, so calls on different streams need a workspace each.
+ * MK_EINVAL: ntrees 0 or > MK_TREES_MAX, an unknown kind, a d_level0 that does
+ * not match the kind, container_len > MK_CONTAINER_MAX, a misaligned,
+ * overflowing or overlapping container_off, a container no tree takes part in,
+ * and each kind's own (item_len == 0, n_new < n_old, n_new > capacity, a bad
+ * field layout, 2^31 work items); MK_ENOMEM: a short workspace.  Every check
+ * comes before any device lookup, and on an error nothing is launched.
+ * Uploads nothing, allocates nothing, never synchronises, and can be captured
+ * into a hipGraph (a linear chain of nodes).
+ * Replaces: ssz.TreeHash (shared/ssz/hash.go:23-239) of a struct whose slice
+ * fields are lists with built trees -- a pb.BeaconState -- after some of their
+ * elements changed. */
+#define MK_TREE_LIST   1   /* mk_dev_ssz_list_tree_update's tree        */
+#define MK_TREE_STRUCT 2   /* mk_dev_ssz_struct_list_tree_update's tree */
+#define MK_TREE_BYTES  3   /* mk_dev_ssz_bytes_list_tree_update's tree  */
+#define MK_TREES_MAX   16
+#define MK_NO_CONTAINER 0xffffffffu
+#define MK_CONTAINER_MAX 4096
+
+typedef struct mk_tree_update {
+    uint32_t kind;
+    uint32_t item_len;        /* item_len / record_len / elem_len */
+    void* d_items;            /* items / records / elements */
+    void* d_level0;           /* STRUCT: d_roots, BYTES: d_digests, LIST: NULL */
+    void* d_levels;
+    uint64_t n_old, n_new, capacity;
+    const uint64_t* d_idx;    /* k_idx strictly ascending indices < n_old, device */
+    uint64_t k_idx;
+    const void* d_values;     /* NULL: already written into d_items on this stream */
+    const mk_field* fields;   /* STRUCT only (host) */
+    uint32_t nfields;
+    uint32_t container_off;   /* byte offset of this tree's root in d_container, or MK_NO_CONTAINER */
+    void* d_root32;           /* this tree's root, always written */
+} mk_tree_update;
+
+uint64_t mk_ssz_trees_update_workspace_bytes(const mk_tree_update* trees, uint32_t ntrees);
+int mk_dev_ssz_trees_update(mk_call* call, const mk_tree_update* trees, uint32_t ntrees, void* d_container,
+                            uint32_t container_len, void* d_container_root32, void* d_ws, uint64_t ws_bytes,
+                            void* stream);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

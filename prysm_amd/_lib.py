@@ -152,6 +152,8 @@ _SIGS = {
     "mk_bytes_list_tree_append": (_int, [_cp, _vp, _vp, _u64]),
     "mk_bytes_list_tree_root": (_int, [_cp, _vp, _vp]),
     "mk_bytes_list_tree_elems": (_int, [_cp, _vp, _u64, _u64, _vp]),
+    "mk_ssz_trees_update_workspace_bytes": (_u64, [_vp, _u32]),
+    "mk_dev_ssz_trees_update": (_int, [_cp, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),
@@ -167,6 +169,26 @@ MK_FIELD_STRUCT = 4    # a nested struct: len = the entries that follow and belo
 class Field(ctypes.Structure):
     """mk_field: one field of a fixed-layout record."""
     _fields_ = [("kind", ctypes.c_uint32), ("offset", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+MK_TREE_LIST = 1    # mk_dev_ssz_list_tree_update's tree
+MK_TREE_STRUCT = 2  # mk_dev_ssz_struct_list_tree_update's tree
+MK_TREE_BYTES = 3   # mk_dev_ssz_bytes_list_tree_update's tree
+MK_TREES_MAX = 16
+MK_NO_CONTAINER = 0xFFFFFFFF
+MK_CONTAINER_MAX = 4096
+# the dirty share from which a resident tree's host handle rebuilds instead of climbing: count / DIV
+# (MK_*_TREE_REBUILD_DIV in csrc/list_tree_api.cpp, struct_tree_api.cpp, bytes_tree_api.cpp)
+LIST_TREE_REBUILD_DIV = 512
+STRUCT_TREE_REBUILD_DIV = 32
+BYTES_TREE_REBUILD_DIV = 256
+
+
+class TreeUpdate(ctypes.Structure):
+    """mk_tree_update: one tree of mk_dev_ssz_trees_update."""
+    _fields_ = [("kind", _u32), ("item_len", _u32), ("d_items", _vp), ("d_level0", _vp), ("d_levels", _vp),
+                ("n_old", _u64), ("n_new", _u64), ("capacity", _u64), ("d_idx", _vp), ("k_idx", _u64),
+                ("d_values", _vp), ("fields", _vp), ("nfields", _u32), ("container_off", _u32), ("d_root32", _vp)]
 
 
 _lib = None

@@ -78,27 +78,34 @@ int dev_build(const void* d_elems, uint64_t n, uint64_t capacity, uint32_t elem_
     return list_tree_build32(d_digests, n, capacity, d_levels, d_root32, d_ws, st);
 }
 
+// Stage 0 of an update, everything before the climb: the new elements
+// scattered in, then level 0 (d_digests) brought up to date -- every digest
+// again for a list of one chunk (it has no levels), else the dirty elements'
+// digests, read in place and stored into level 0.  (Digest and climb in one
+// launch -- the level-1 owner pairs digesting their own elements -- were built
+// and measured no faster at any k: DESIGN.md §5f.)
+int stage0(void* d_elems, uint64_t n_old, uint64_t n_new, uint32_t elem_len, void* d_digests, const uint64_t* d_idx,
+           uint64_t k_idx, const void* d_values, hipStream_t st) {
+    const uint64_t n_app = n_new - n_old, T = k_idx + n_app;
+    if (d_values) TRY(list_tree_scatter(d_elems, d_idx, k_idx, n_old, n_app, elem_len, d_values, st));
+    if (bt_chunks(n_new) <= 1) return launch_elem_digests(d_elems, n_new, elem_len, d_digests, st);
+    if (T == 0) return MK_OK;  // nothing changed
+    const uint32_t fast32 = elem_len == 32 && ((uintptr_t)d_elems % 16) == 0;
+    hipLaunchKernelGGL(mk::k_bytes_tree_digest, dim3(ceil_div(T, 256)), dim3(256), 0, st, (const uint8_t*)d_elems,
+                       elem_len, fast32, d_idx, k_idx, n_old, n_app, (uint4*)d_digests);
+    return launched();
+}
+
 int dev_update(void* d_elems, uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t elem_len, void* d_digests,
                void* d_levels, const uint64_t* d_idx, uint64_t k_idx, const void* d_values, void* d_root32,
                void* d_ws, hipStream_t st) {
-    const uint64_t n_app = n_new - n_old, T = k_idx + n_app;
-    if (d_values) TRY(list_tree_scatter(d_elems, d_idx, k_idx, n_old, n_app, elem_len, d_values, st));
-    if (bt_chunks(n_new) <= 1) {  // one chunk, no levels: every digest again, the mix-in over the raw chunk
-        TRY(launch_elem_digests(d_elems, n_new, elem_len, d_digests, st));
+    TRY(stage0(d_elems, n_old, n_new, elem_len, d_digests, d_idx, k_idx, d_values, st));
+    if (bt_chunks(n_new) <= 1) {  // one chunk, no levels: the mix-in over the raw chunk of digests
         hipLaunchKernelGGL(mk::k_final_small, dim3(1), dim3(64), 0, st, (const uint8_t*)d_digests, 32 * n_new, n_new,
                            (uint8_t*)d_root32);
         return launched();
     }
-    if (T == 0)  // nothing changed: the root again, from the stored top node
-        return list_tree_update32(d_digests, d_levels, nullptr, 0, n_new, n_new, capacity, d_root32, d_ws, st);
-    // The dirty elements' digests, read in place and stored into the tree's
-    // level 0, then the list tree's update.  (The same two stages in one
-    // launch -- the level-1 owner pairs digesting their own elements -- were
-    // built and measured no faster at any k: DESIGN.md §5f.)
-    const uint32_t fast32 = elem_len == 32 && ((uintptr_t)d_elems % 16) == 0;
-    hipLaunchKernelGGL(mk::k_bytes_tree_digest, dim3(ceil_div(T, 256)), dim3(256), 0, st, (const uint8_t*)d_elems,
-                       elem_len, fast32, d_idx, k_idx, n_old, n_app, (uint4*)d_digests);
-    HIPCHK(hipGetLastError());
+    // the list tree's update (with nothing changed: the root again, from the stored top node)
     return list_tree_update32(d_digests, d_levels, d_idx, k_idx, n_old, n_new, capacity, d_root32, d_ws, st);
 }
 
@@ -238,6 +245,22 @@ int tree_elems(mk_bytes_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out
 }
 
 }  // namespace
+
+// the bytes tree's part of mk_dev_ssz_trees_update (tree_many_api.cpp)
+namespace mk::rt {
+int bytes_tree_check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t elem_len, uint64_t k_idx,
+                            uint64_t ws_bytes) {
+    return check_update(n_old, n_new, capacity, elem_len, k_idx, ws_bytes);
+}
+int bytes_tree_check_ptrs(const void* d_elems, uint64_t n, uint64_t capacity, const void* d_digests,
+                          const void* d_levels, const void* d_root32, const void* d_ws) {
+    return check_ptrs(d_elems, n, capacity, d_digests, d_levels, d_root32, d_ws);
+}
+int bytes_tree_stage0(void* d_elems, uint64_t n_old, uint64_t n_new, uint32_t elem_len, void* d_digests,
+                      const uint64_t* d_idx, uint64_t k_idx, const void* d_values, hipStream_t st) {
+    return stage0(d_elems, n_old, n_new, elem_len, d_digests, d_idx, k_idx, d_values, st);
+}
+}  // namespace mk::rt
 
 extern "C" {
 

@@ -50,9 +50,10 @@ int lt_check(uint64_t n, uint64_t capacity, uint32_t item_len) {
     return MK_OK;
 }
 
-int launch_update(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
-                  uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32, void* d_ws, hipStream_t st) {
-    const uint64_t T = k_idx + (n_new - n_old);
+// the climb's descriptor (k_list_tree_update, one slice of k_trees_update); d_arrive: zeroed arrival words
+mk::ListTreeArgs update_args(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
+                             uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32,
+                             void* d_arrive) {
     mk::ListTreeArgs a{};
     a.items = (const uint8_t*)d_items;
     a.levels = (uint32_t*)d_levels;
@@ -63,8 +64,16 @@ int launch_update(const void* d_items, void* d_levels, const uint64_t* d_idx, ui
     a.cap_chunks = lt_chunks(capacity, item_len);
     a.item_len = item_len;
     a.per = (uint32_t)lt_per(item_len);
-    a.arrive = (uint64_t*)d_ws;
+    a.arrive = (uint64_t*)d_arrive;
     a.root_out = (uint32_t*)d_root32;
+    return a;
+}
+
+int launch_update(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
+                  uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32, void* d_ws, hipStream_t st) {
+    const uint64_t T = k_idx + (n_new - n_old);
+    const mk::ListTreeArgs a =
+        update_args(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_ws);
     HIPCHK(hipMemsetAsync(d_ws, 0, 8 * std::max<uint64_t>(T, 1), st));
     hipLaunchKernelGGL(mk::k_list_tree_update, dim3(std::max<uint64_t>(ceil_div(2 * T, 256), 1)), dim3(256), 0, st, a);
     return launched();
@@ -293,6 +302,20 @@ int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_id
 int list_tree_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
                       uint32_t item_len, const void* d_values, hipStream_t st) {
     return launch_scatter(d_items, d_idx, k_idx, n_old, n_app, item_len, d_values, st);
+}
+// the list tree's part of mk_dev_ssz_trees_update (its stage 0 is list_tree_scatter alone)
+int list_tree_check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, uint64_t k_idx,
+                           uint64_t ws_bytes) {
+    return check_update(n_old, n_new, capacity, item_len, k_idx, ws_bytes);
+}
+int list_tree_check_ptrs(const void* d_items, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
+                         const void* d_root32, const void* d_ws) {
+    return check_ptrs(d_items, n, capacity, item_len, d_levels, d_root32, d_ws);
+}
+mk::ListTreeArgs list_tree_args(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
+                                uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32,
+                                void* d_arrive) {
+    return update_args(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_arrive);
 }
 }  // namespace mk::rt
 

@@ -4309,20 +4309,18 @@ __device__ __forceinline__ void lt_load_node(const uint32_t* lv, uint64_t j, uin
     }
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(256) void k_list_tree_update(ListTreeArgs a) {
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t t = gid >> 1;
-    const uint32_t p = (uint32_t)(gid & 1u);
+// The climb of one tree by the lane pair (t, p) of work item t: the body of
+// k_list_tree_update and of one tree's slice of k_trees_update.  True in the
+// one pair that stored the root, whose parity words it leaves in r.
+__device__ __forceinline__ bool lt_update(const ListTreeArgs& a, uint64_t t, uint32_t p, uint32_t (&r)[4]) {
     const uint64_t T = a.k_idx + (a.n_new - a.n_old);
     const uint64_t cb = (uint64_t)a.per * a.item_len, total = a.n_new * a.item_len;
-    const uint64_t nch = (a.n_new + a.per - 1) / a.per;  // >= 2 (the host runs smaller lists through k_final_small)
+    const uint64_t nch = (a.n_new + a.per - 1) / a.per;  // >= 2 (smaller lists: k_final_small, k_trees_update itself)
     uint64_t cnt = (nch + 1) >> 1, off = 0, capd = (a.cap_chunks + 1) >> 1;  // level d: nodes, offset, room
     uint32_t d = 1;
     uint32_t h[4];
     if (T == 0) {  // nothing changed: the root again, from the stored top node
-        if (t != 0) return;
+        if (t != 0) return false;
         while (cnt > 1) {
             off += capd;
             capd = (capd + 1) >> 1;
@@ -4330,9 +4328,9 @@ __global__ __launch_bounds__(256) void k_list_tree_update(ListTreeArgs a) {
         }
         lt_load_node(a.levels + 8 * off, 0, p, h);
     } else {
-        if (t >= T) return;
+        if (t >= T) return false;
         uint64_t j = lt_chunk(a, t) >> 1;
-        if (t > 0 && (lt_chunk(a, t - 1) >> 1) == j) return;  // not the first work item of its level-1 node
+        if (t > 0 && (lt_chunk(a, t - 1) >> 1) == j) return false;  // not the first work item of its level-1 node
         uint64_t o = t, e = lt_upper(a, t + 1, T, 1, j);
         {  // level-1 node j: bytes [2 j cb, min(total, (2 j + 2) cb)), then 0^128 when chunk 2 j + 1 is absent
             const uint64_t b0 = 2 * j * cb;
@@ -4374,18 +4372,18 @@ __global__ __launch_bounds__(256) void k_list_tree_update(ListTreeArgs a) {
                     second = (uint32_t)(old >> d) & 1u;
                 }
                 second |= (uint32_t)__shfl_xor((int)second, 1);
-                if (!second) return;  // first to arrive: the sibling's pair hashes the parent
-                __threadfence();      // acquire: the sibling's stores before the loads below
+                if (!second) return false;  // first to arrive: the sibling's pair hashes the parent
+                __threadfence();           // acquire: the sibling's stores before the loads below
             }
-            uint32_t s[4] = {0u, 0u, 0u, 0u}, r[4];
+            uint32_t s[4] = {0u, 0u, 0u, 0u}, q[4];
             const bool padded = sib >= cnt;  // only ever a missing RIGHT child
             if (!padded) lt_load_node(lv, sib, p, s);
             if (right)
-                hash_pair3(s, h, false, p, r);
+                hash_pair3(s, h, false, p, q);
             else
-                hash_pair3(h, s, padded, p, r);
+                hash_pair3(h, s, padded, p, q);
 #pragma unroll
-            for (int w = 0; w < 4; ++w) h[w] = r[w];
+            for (int w = 0; w < 4; ++w) h[w] = q[w];
             j >>= 1;
             off += capd;
             capd = (capd + 1) >> 1;
@@ -4394,9 +4392,108 @@ __global__ __launch_bounds__(256) void k_list_tree_update(ListTreeArgs a) {
         }
     }
     // root = K(top || le64(n) || 0^24) (hash.go:237-238)
-    uint32_t m[4] = {ilv::to_ilv((uint32_t)a.n_new, (uint32_t)(a.n_new >> 32), p), 0u, 0u, 0u}, r[4];
+    uint32_t m[4] = {ilv::to_ilv((uint32_t)a.n_new, (uint32_t)(a.n_new >> 32), p), 0u, 0u, 0u};
     hash_pair3(h, m, false, p, r);
     store_node3(a.root_out, 0, false, p, r);
+    return true;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_list_tree_update(ListTreeArgs a) {
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t r[4];
+    (void)lt_update(a, gid >> 1, (uint32_t)(gid & 1u), r);
+}
+
+// ----------------------------------------------------------------------------
+// Several resident trees in one launch: slice blockIdx.y of
+// the grid is k_list_tree_update over tree g.t[blockIdx.y] -- the descriptors
+// travel by value in the kernel arguments, nothing is uploaded.  A tree of at
+// most one chunk has no levels: the first pair of its slice hashes the raw
+// chunk with the mix-in, as k_final_small does.
+// Container (hash.go:141-159, a struct whose list fields are these trees): the
+// pair that stores tree i's root also stores it at container + coff[i]; the
+// last of the nparts participating trees to arrive hashes the whole container
+// message.  Ordering contract, the one of the climb's hand-off: root stores ->
+// __threadfence() (agent release) -> acq_rel agent-scope atomic add on the
+// counter (zeroed on the stream by the same call); the last arriver: that
+// atomic -> __threadfence() (agent acquire) -> agent-scope loads of the
+// container.  Exactly one pair per tree arrives and none waits, so the launch
+// completes whatever the dispatch order.
+namespace {
+
+// K(p[0, len)), p 4-B aligned, every byte by an agent-scope load
+__device__ __noinline__ void sponge_acquired(const uint8_t* p, uint32_t len, uint4& d0, uint4& d1) {
+    const uint32_t nb = len / 136 + 1;
+    State s;
+    zero(s);
+    for (uint32_t b = 0; b < nb; ++b) {
+#pragma unroll
+        for (int w = 0; w < 17; ++w) {
+            uint32_t v[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t m = b * 136 + 8u * w + 4u * h;
+                uint32_t x = 0;
+                if (m + 4 <= len) {
+                    x = __hip_atomic_load(reinterpret_cast<const uint32_t*>(p + m), __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+#pragma unroll 1
+                    for (uint32_t k = 0; m + k < len; ++k)  // the last 1..3 bytes
+                        x |= (uint32_t)__hip_atomic_load(p + m + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                             << (8 * k);
+                }
+                if (m <= len && len < m + 4) x ^= 1u << (8 * (len - m));  // domain pad byte 0x01
+                v[h] = x;
+            }
+            if (b == nb - 1 && w == 16) v[1] ^= 0x80000000u;
+            s.lo[w] ^= v[0];
+            s.hi[w] ^= v[1];
+        }
+        keccak_f(s);
+    }
+    digest(s, d0, d1);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_trees_update(TreesArgs g) {
+    const ListTreeArgs& a = g.t[blockIdx.y];
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t = gid >> 1;
+    const uint32_t p = (uint32_t)(gid & 1u);
+    uint32_t r[4];
+    if ((a.n_new + a.per - 1) / a.per <= 1) {  // no levels: root = K(raw chunk (0^128 when empty) || le64(n) || 0^24)
+        if (t != 0) return;
+        uint4 d0, d1;
+        sponge_generic(a.items, a.n_new * a.item_len, a.n_new == 0 ? 128u : 0u, true, a.n_new, d0, d1);
+        r[0] = ilv::to_ilv(d0.x, d0.y, p);
+        r[1] = ilv::to_ilv(d0.z, d0.w, p);
+        r[2] = ilv::to_ilv(d1.x, d1.y, p);
+        r[3] = ilv::to_ilv(d1.z, d1.w, p);
+        store_node3(a.root_out, 0, false, p, r);
+    } else if (!lt_update(a, t, p, r)) {
+        return;
+    }
+    const uint32_t coff = g.coff[blockIdx.y];
+    if (coff == 0xffffffffu) return;  // this tree is no field of the container
+    store_node3(reinterpret_cast<uint32_t*>(g.container + coff), 0, false, p, r);
+    __threadfence();  // release: this pair's root stores before its arrival
+    uint32_t last = 0;
+    if (p == 0)
+        last = __hip_atomic_fetch_add(g.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == g.nparts;
+    last |= (uint32_t)__shfl_xor((int)last, 1);
+    if (!last) return;
+    __threadfence();  // acquire: every tree's root stores before the loads of the container
+    uint4 d0, d1;
+    sponge_acquired(g.container, g.container_len, d0, d1);
+    if (p == 0) {
+        const uint32_t d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+        for (int w = 0; w < 8; ++w) g.container_root[w] = d[w];
+    }
 }
 
 // list[idx[v]] = values[v] for v < k_idx (an index >= n_old is skipped), then

@@ -184,6 +184,19 @@ struct ListTreeArgs {
 };
 // one lane pair per dirty item; the ancestors of the dirty chunks and the root
 __global__ void k_list_tree_update(ListTreeArgs a);
+// several resident trees in one launch (tree_many_api.cpp): the descriptors by value, 1.4 KB of kernel arguments
+constexpr uint32_t kTreesMax = 16;
+struct TreesArgs {
+    ListTreeArgs t[kTreesMax];  // tree blockIdx.y; at most one chunk (no levels): root over the raw chunk
+    uint32_t coff[kTreesMax];   // byte offset (4-B aligned) of the tree's root in the container, 0xffffffff: none
+    uint8_t* container;         // the struct's hash message (4-B aligned), NULL: no container
+    uint32_t* counter;          // zeroed; the nparts participating trees arrive here
+    uint32_t* container_root;   // K(container[0, container_len)), by the last tree to arrive
+    uint32_t container_len;
+    uint32_t nparts;
+};
+// grid (blocks of the largest tree, ntrees): slice y is k_list_tree_update over t[y], then the container
+__global__ void k_trees_update(TreesArgs g);
 __global__ void k_list_tree_scatter(uint8_t* items, const uint64_t* idx, uint64_t k_idx, uint64_t n_old,
                                     uint64_t n_app, uint32_t item_len, uint32_t unit, const uint8_t* vals);
 // device-resident registry tree (struct_tree_api.cpp): the dirty records side by side

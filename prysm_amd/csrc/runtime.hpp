@@ -174,6 +174,39 @@ int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_id
 int list_tree_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
                       uint32_t item_len, const void* d_values, hipStream_t st);
 
+// ---- one tree of mk_dev_ssz_trees_update (tree_many_api.cpp) ----------------------------
+// What each kind's own update entry point runs, shared with the call over
+// several trees: its host-checkable arguments, its pointer checks, its stage 0
+// (every launch before the climb: the values scattered in, level 0 brought up
+// to date) and the climb's descriptor.
+int list_tree_check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, uint64_t k_idx,
+                           uint64_t ws_bytes);
+int list_tree_check_ptrs(const void* d_items, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
+                         const void* d_root32, const void* d_ws);
+mk::ListTreeArgs list_tree_args(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
+                                uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32,
+                                void* d_arrive);
+struct StructTreeLayout {
+    mk::HostSpec sp;
+    bool fused;    // the struct-roots launch needs no message buffer (k_struct_fused, k_struct_nested)
+    uint32_t ext;  // bytes of a record the fields reach, rounded up to 4 (<= rec_len)
+};
+int struct_tree_layout(const mk_field* fields, uint32_t nfields, uint32_t record_len, StructTreeLayout& L);
+// the update workspace for k work items; *arrive_bytes: its leading part, the arrival words (the rest is scratch)
+uint64_t struct_tree_update_ws(const StructTreeLayout& L, uint64_t k, uint64_t* arrive_bytes);
+int struct_tree_check_update(const StructTreeLayout& L, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                             uint64_t k_idx, uint64_t ws_bytes);
+int struct_tree_check_ptrs(const void* d_records, uint64_t n, uint64_t capacity, const void* d_roots,
+                           const void* d_levels, const void* d_root32, const void* d_ws);
+int struct_tree_stage0(const StructTreeLayout& L, void* d_records, uint64_t n_old, uint64_t n_new, void* d_roots,
+                       const uint64_t* d_idx, uint64_t k_idx, const void* d_values, void* d_scratch, hipStream_t st);
+int bytes_tree_check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t elem_len, uint64_t k_idx,
+                            uint64_t ws_bytes);
+int bytes_tree_check_ptrs(const void* d_elems, uint64_t n, uint64_t capacity, const void* d_digests,
+                          const void* d_levels, const void* d_root32, const void* d_ws);
+int bytes_tree_stage0(void* d_elems, uint64_t n_old, uint64_t n_new, uint32_t elem_len, void* d_digests,
+                      const uint64_t* d_idx, uint64_t k_idx, const void* d_values, hipStream_t st);
+
 // ---- multi-device (multi_api.cpp) ------------------------------------------------
 int host_merkle_multi(const uint8_t* items, uint64_t n, uint32_t item_len, int nshards, const int* devs_in,
                       uint8_t* out, uint32_t elem_len = 0);

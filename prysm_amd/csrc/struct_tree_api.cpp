@@ -9,13 +9,7 @@ using namespace mk;
 using namespace mk::rt;
 
 // ---- registry tree handle ----------------------------------------------------------------
-namespace {
-struct Layout {
-    mk::HostSpec sp;
-    bool fused;    // the struct-roots launch needs no message buffer (k_struct_fused, k_struct_nested)
-    uint32_t ext;  // bytes of a record the fields reach, rounded up to 4 (<= rec_len)
-};
-}  // namespace
+using Layout = mk::rt::StructTreeLayout;
 
 struct mk_struct_list_tree {
     std::mutex mu;
@@ -114,45 +108,49 @@ int dev_build(const Layout& L, const void* d_records, uint64_t n, uint64_t capac
     return list_tree_build32(d_roots, n, capacity, d_levels, d_root32, (uint8_t*)d_ws + msg_bytes(L, n), st);
 }
 
-// An update: the dirty records side by side, their roots by the struct-roots
-// launch, the roots scattered into the tree's level 0, the list tree's update.
+// Stage 0 of an update, everything before the climb: the new records scattered
+// in, then level 0 (d_roots) brought up to date -- every root again for a list
+// of one chunk (it has no levels), else the dirty records side by side, their
+// roots by the struct-roots launch, the roots scattered into level 0.
+// `scratch`: the update workspace from UpdateWs::gath on.
 // (One fused launch -- struct root, arrival count per window, climb -- was
 // built and measured slower than this at every k: DESIGN.md §5e.)
-int launch_composed(const Layout& L, const void* d_records, uint64_t n_old, uint64_t n_new, uint64_t capacity,
-                    void* d_roots, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, const void* d_values,
-                    void* d_root32, void* d_ws, hipStream_t st) {
+int stage0(const Layout& L, void* d_records, uint64_t n_old, uint64_t n_new, void* d_roots, const uint64_t* d_idx,
+           uint64_t k_idx, const void* d_values, uint8_t* scratch, hipStream_t st) {
     const uint64_t n_app = n_new - n_old, T = k_idx + n_app;
     const UpdateWs w = update_ws(L, T);
-    uint8_t* ws = (uint8_t*)d_ws;
+    uint8_t* gath = scratch;
+    uint8_t* msg = scratch + (w.msg - w.gath);
+    uint8_t* roots = scratch + (w.roots - w.gath);
+    if (d_values) TRY(list_tree_scatter(d_records, d_idx, k_idx, n_old, n_app, L.sp.rec_len, d_values, st));
+    if (st_chunks(n_new) <= 1) return struct_launch_roots(d_records, n_new, L.sp, msg, d_roots, st);
+    if (T == 0) return MK_OK;  // nothing changed
     mk::HostSpec sp = L.sp;
     const void* src = d_values;  // holds them in work-item order already
     if (!src) {
         hipLaunchKernelGGL(mk::k_struct_tree_gather, dim3(ceil_div(T * (L.ext / 4), 256)), dim3(256), 0, st,
-                           (const uint8_t*)d_records, d_idx, k_idx, n_old, n_app, L.sp.rec_len, L.ext, ws + w.gath);
+                           (const uint8_t*)d_records, d_idx, k_idx, n_old, n_app, L.sp.rec_len, L.ext, gath);
         HIPCHK(hipGetLastError());
-        src = ws + w.gath;
+        src = gath;
         sp.rec_len = sp.prog.rec_len = L.ext;
     }
-    TRY(struct_launch_roots(src, T, sp, ws + w.msg, ws + w.roots, st));
-    TRY(list_tree_scatter(d_roots, d_idx, k_idx, n_old, n_app, 32, ws + w.roots, st));
-    return list_tree_update32(d_roots, d_levels, d_idx, k_idx, n_old, n_new, capacity, d_root32, ws + w.arrive, st);
+    TRY(struct_launch_roots(src, T, sp, msg, roots, st));
+    return list_tree_scatter(d_roots, d_idx, k_idx, n_old, n_app, 32, roots, st);
 }
 
 int dev_update(const Layout& L, void* d_records, uint64_t n_old, uint64_t n_new, uint64_t capacity, void* d_roots,
                void* d_levels, const uint64_t* d_idx, uint64_t k_idx, const void* d_values, void* d_root32,
                void* d_ws, hipStream_t st) {
-    const uint64_t n_app = n_new - n_old, T = k_idx + n_app;
-    if (d_values) TRY(list_tree_scatter(d_records, d_idx, k_idx, n_old, n_app, L.sp.rec_len, d_values, st));
-    if (st_chunks(n_new) <= 1) {  // one chunk, no levels: every root again, the mix-in over the raw chunk
-        TRY(struct_launch_roots(d_records, n_new, L.sp, (uint8_t*)d_ws + update_ws(L, T).msg, d_roots, st));
+    const UpdateWs w = update_ws(L, k_idx + (n_new - n_old));
+    TRY(stage0(L, d_records, n_old, n_new, d_roots, d_idx, k_idx, d_values, (uint8_t*)d_ws + w.gath, st));
+    if (st_chunks(n_new) <= 1) {  // one chunk, no levels: the mix-in over the raw chunk of roots
         hipLaunchKernelGGL(mk::k_final_small, dim3(1), dim3(64), 0, st, (const uint8_t*)d_roots, 32 * n_new, n_new,
                            (uint8_t*)d_root32);
         return launched();
     }
-    if (T == 0)  // nothing changed: the root again, from the stored top node
-        return list_tree_update32(d_roots, d_levels, nullptr, 0, n_new, n_new, capacity, d_root32, d_ws, st);
-    return launch_composed(L, d_records, n_old, n_new, capacity, d_roots, d_levels, d_idx, k_idx, d_values, d_root32,
-                           d_ws, st);
+    // the list tree's update (with nothing changed: the root again, from the stored top node)
+    return list_tree_update32(d_roots, d_levels, d_idx, k_idx, n_old, n_new, capacity, d_root32,
+                              (uint8_t*)d_ws + w.arrive, st);
 }
 
 // ---- handle ------------------------------------------------------------------------------
@@ -294,6 +292,31 @@ int tree_records(mk_struct_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* 
 }
 
 }  // namespace
+
+// the registry tree's part of mk_dev_ssz_trees_update (tree_many_api.cpp)
+namespace mk::rt {
+int struct_tree_layout(const mk_field* fields, uint32_t nfields, uint32_t record_len, StructTreeLayout& L) {
+    return st_layout(fields, nfields, record_len, L);
+}
+uint64_t struct_tree_update_ws(const StructTreeLayout& L, uint64_t k, uint64_t* arrive_bytes) {
+    const UpdateWs w = update_ws(L, k);
+    *arrive_bytes = w.gath;
+    return w.total;
+}
+int struct_tree_check_update(const StructTreeLayout& L, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                             uint64_t k_idx, uint64_t ws_bytes) {
+    if (L.sp.rec_len == 0) return fail(MK_EINVAL, "record_len == 0");
+    return check_update(L, n_old, n_new, capacity, k_idx, ws_bytes);
+}
+int struct_tree_check_ptrs(const void* d_records, uint64_t n, uint64_t capacity, const void* d_roots,
+                           const void* d_levels, const void* d_root32, const void* d_ws) {
+    return check_ptrs(d_records, n, capacity, d_roots, d_levels, d_root32, d_ws);
+}
+int struct_tree_stage0(const StructTreeLayout& L, void* d_records, uint64_t n_old, uint64_t n_new, void* d_roots,
+                       const uint64_t* d_idx, uint64_t k_idx, const void* d_values, void* d_scratch, hipStream_t st) {
+    return stage0(L, d_records, n_old, n_new, d_roots, d_idx, k_idx, d_values, (uint8_t*)d_scratch, st);
+}
+}  // namespace mk::rt
 
 extern "C" {
 

@@ -666,6 +666,85 @@ def bytes_list_tree_update(elems: torch.Tensor, n_old: int, n_new: int, capacity
     return root
 
 
+class TreeArgs:
+    """One tree of ``trees_update`` (mk_tree_update): the arguments of that
+    kind's own ``*_tree_update`` wrapper.  ``kind`` is _lib.MK_TREE_LIST /
+    STRUCT / BYTES; ``level0`` the struct roots (STRUCT) or element digests
+    (BYTES); ``spec`` the field layout (STRUCT); ``container_off`` the byte
+    offset of the tree's root in the container message, None: not a field of
+    it."""
+
+    def __init__(self, kind: int, items: torch.Tensor, n_old: int, n_new: int, capacity: int, item_len: int,
+                 levels: torch.Tensor, root: torch.Tensor, level0: torch.Tensor = None, idx: torch.Tensor = None,
+                 k_idx: int = 0, values: torch.Tensor = None, spec=None, container_off: int = None):
+        self.kind, self.items, self.n_old, self.n_new, self.capacity = kind, items, n_old, n_new, capacity
+        self.item_len, self.levels, self.root, self.level0, self.idx = item_len, levels, root, level0, idx
+        self.k_idx, self.values, self.spec, self.container_off = k_idx, values, spec, container_off
+
+
+def _tree_table(trees):
+    """The mk_tree_update array of ``trees`` (and what it points to, kept alive by the caller)."""
+    from .registry import _fields
+
+    arr = (_lib.TreeUpdate * max(len(trees), 1))()
+    keep = []
+    for a, t in zip(arr, trees):
+        if t.items.numel() * t.items.element_size() < t.n_new * t.item_len:
+            raise ValueError("item buffer shorter than n_new * item_len")
+        if t.k_idx and (t.idx is None or t.idx.numel() < t.k_idx or t.idx.element_size() != 8):
+            raise ValueError("idx: k_idx 64-bit device indices")
+        k = t.k_idx + max(t.n_new - t.n_old, 0)
+        if t.values is not None and t.values.numel() * t.values.element_size() < k * t.item_len:
+            raise ValueError("values shorter than (k_idx + appended) * item_len")
+        if t.level0 is not None and t.level0.numel() < 32 * t.n_new:
+            raise ValueError("level-0 buffer shorter than 32 * n_new")
+        a.kind, a.item_len = t.kind, t.item_len
+        a.d_items = t.items.data_ptr()
+        a.d_level0 = t.level0.data_ptr() if t.level0 is not None else None
+        a.d_levels = t.levels.data_ptr() if t.levels is not None else None
+        a.n_old, a.n_new, a.capacity = t.n_old, t.n_new, t.capacity
+        a.d_idx = t.idx.data_ptr() if t.k_idx else None
+        a.k_idx = t.k_idx
+        a.d_values = t.values.data_ptr() if t.values is not None else None
+        if t.spec is not None:
+            f = _fields(t.spec)
+            keep.append(f)
+            a.fields, a.nfields = ctypes.cast(f, ctypes.c_void_p), len(t.spec)
+        a.container_off = _lib.MK_NO_CONTAINER if t.container_off is None else t.container_off
+        a.d_root32 = t.root.data_ptr()
+    return arr, keep
+
+
+def trees_update_workspace_bytes(trees) -> int:
+    """Workspace of ``trees_update`` over ``trees`` (0: a list it would refuse)."""
+    arr, _keep = _tree_table(trees)
+    return _lib.load().mk_ssz_trees_update_workspace_bytes(arr, len(trees))
+
+
+def trees_update(trees, container: torch.Tensor = None, container_len: int = 0,
+                 container_root: torch.Tensor = None, ws: torch.Tensor = None) -> None:
+    """Update up to 16 resident trees (``TreeArgs``) in one call: each tree's
+    stage 0, then one launch in which all of them climb.  Every tree ends as
+    its own ``*_tree_update`` would leave it, its root in ``t.root``.  With
+    ``container_len`` > 0, ``container`` is the hash message of the struct
+    that holds the trees: each root is also written at its ``container_off``
+    and Keccak(container[:container_len]) lands in ``container_root``, all
+    in the same launch (mk_dev_ssz_trees_update)."""
+    if not trees:
+        raise ValueError("no trees")
+    dev = _dev(trees[0].items)
+    arr, _keep = _tree_table(trees)
+    if ws is None:
+        ws = torch.empty(_lib.load().mk_ssz_trees_update_workspace_bytes(arr, len(trees)), dtype=torch.uint8,
+                         device=trees[0].items.device)
+    if container_len and (container is None or container.numel() < container_len or container_root is None or
+                          container_root.numel() < 32):
+        raise ValueError("container shorter than container_len, or no 32-B container root")
+    _lib.invoke("mk_dev_ssz_trees_update", arr, len(trees), _p(container) if container_len else None, container_len,
+                _p(container_root) if container_len else None, _p(ws), ws.numel(), _stream(trees[0].items.device),
+                device=dev)
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

@@ -392,3 +392,311 @@ def synthetic_state(n_validators: int, seed: int, n_attestations: int = 128, n_b
     sc = u64(len(_SCALARS))
     st.scalars = {name: int(x) for name, x in zip(_SCALARS, sc)}
     return st
+
+
+# ---------------------------------------------------------------- the resident state
+# offset of every field output in the state's 536-B hash message (tree_hash_ssz step 5)
+def _container_layout():
+    offs, pos = {}, 0
+    for name, typ in STATE_FIELDS[:25]:
+        offs[name] = pos
+        pos += 8 if typ is _U64 else 32
+    return offs, pos
+
+
+CONTAINER_OFF, CONTAINER_LEN = _container_layout()
+
+# the ten list fields in STATE_FIELDS order: (BeaconState attribute, state field, tree kind, item length, layout)
+_K_LIST, _K_STRUCT, _K_BYTES = _lib.MK_TREE_LIST, _lib.MK_TREE_STRUCT, _lib.MK_TREE_BYTES
+RESIDENT_TREES = [
+    ("registry", "ValidatorRegistry", _K_STRUCT, R.VALIDATOR_DTYPE.itemsize, R.VALIDATOR_FIELDS),
+    ("balances", "ValidatorBalances", _K_LIST, 8, None),
+    ("randao_mixes", "LatestRandaoMixesHash32S", _K_BYTES, 32, None),
+    ("crosslinks", "LatestCrosslinks", _K_STRUCT, 40, CROSSLINK_FIELDS),
+    ("latest_block_roots", "LatestBlockRootHash32S", _K_BYTES, 32, None),
+    ("batched_block_roots", "BatchedBlockRootHash32S", _K_BYTES, 32, None),
+    ("penalized_balances", "LatestPenalizedBalances", _K_LIST, 8, None),
+    ("attestations", "LatestAttestations", _K_STRUCT, pending_attestation_record_len(48), PENDING_ATTESTATION_FIELDS),
+    ("index_roots", "LatestIndexRootHash32S", _K_BYTES, 32, None),
+    ("eth1_votes", "Eth1DataVotes", _K_STRUCT, 72, ETH1_VOTE_FIELDS),
+]
+# the dirty share from which each kind's host handle rebuilds instead of climbing
+_REBUILD_DIV = {_K_LIST: _lib.LIST_TREE_REBUILD_DIV, _K_STRUCT: _lib.STRUCT_TREE_REBUILD_DIV,
+                _K_BYTES: _lib.BYTES_TREE_REBUILD_DIV}
+
+
+def widen_attestation_records(rec: np.ndarray, old_cap: int, new_cap: int) -> np.ndarray:
+    """Packed PendingAttestationRecords moved to bitfield slots of ``new_cap`` bytes."""
+    so, sn = 4 + old_cap, 4 + new_cap
+    out = np.zeros((rec.shape[0], pending_attestation_record_len(new_cap)), dtype=np.uint8)
+    out[:, :192] = rec[:, :192]
+    out[:, 192:192 + so] = rec[:, 192:192 + so]
+    out[:, 192 + sn:192 + sn + so] = rec[:, 192 + so:192 + 2 * so]
+    out[:, 192 + 2 * sn:] = rec[:, 192 + 2 * so:]
+    return out
+
+
+class _ResidentTree:
+    """One list of the resident state: its items, level 0, levels and root in
+    HBM, and the changes made since the last root (host side)."""
+
+    def __init__(self, kind: int, item_len: int, spec, device):
+        self.kind, self.item_len, self.spec, self.device = kind, item_len, spec, device
+        self.n = self.cap = 0
+        self.items = self.level0 = self.levels = None
+        import torch
+
+        self.root = torch.zeros(32, dtype=torch.uint8, device=device)
+        self.pending = {}    # index -> row, the last value of a repeated index
+        self.appended = []   # rows
+
+    def __len__(self):
+        return self.n + len(self.appended)
+
+    def _rows(self, values) -> np.ndarray:
+        a = np.ascontiguousarray(values)
+        a = a.view(np.uint8) if a.dtype != np.uint8 else a
+        if a.size % self.item_len:
+            raise ValueError(f"{a.size} bytes are not a whole number of {self.item_len}-byte items")
+        return a.reshape(-1, self.item_len)
+
+    def _alloc(self, cap: int) -> None:
+        import torch
+
+        from . import device as D
+
+        self.cap = cap
+        self.items = torch.zeros(cap * self.item_len + 16, dtype=torch.uint8, device=self.device)
+        len0 = self.item_len
+        if self.kind != _K_LIST:
+            self.level0 = torch.zeros(32 * cap + 16, dtype=torch.uint8, device=self.device)
+            len0 = 32
+        self.levels = torch.zeros(max(D.list_tree_levels_bytes(cap, len0), 16), dtype=torch.uint8, device=self.device)
+
+    def _build(self) -> None:
+        from . import device as D
+
+        if self.kind == _K_LIST:
+            D.list_tree_build(self.items, self.n, self.cap, self.item_len, self.levels, self.root)
+        elif self.kind == _K_STRUCT:
+            D.struct_list_tree_build(self.items, self.n, self.cap, self.item_len, self.spec, self.level0, self.levels,
+                                     self.root)
+        else:
+            D.bytes_list_tree_build(self.items, self.n, self.cap, self.item_len, self.level0, self.levels, self.root)
+
+    def replace(self, values) -> None:
+        """Any new content, through the build entry."""
+        import torch
+
+        rows = self._rows(values)
+        n = rows.shape[0]
+        if self.items is None or n > self.cap:
+            self._alloc(max(n, 1))
+        if n:
+            self.items[:n * self.item_len].copy_(torch.from_numpy(rows.reshape(-1)))
+        self.n = n
+        self.pending, self.appended = {}, []
+        self._build()
+
+    def update(self, indices, values) -> None:
+        idx = [int(i) for i in np.asarray(indices).reshape(-1)]
+        rows = self._rows(values)
+        if len(idx) != rows.shape[0]:
+            raise ValueError("one value per index")
+        for i in idx:
+            if i < 0 or i >= len(self):
+                raise IndexError(f"index {i} beyond {len(self)} items")
+        for i, row in zip(idx, rows):
+            if i >= self.n:
+                self.appended[i - self.n] = row.copy()
+            else:
+                self.pending[i] = row.copy()
+
+    def append(self, values) -> None:
+        self.appended.extend(r.copy() for r in self._rows(values))
+
+    def _write_through(self) -> None:
+        """The pending changes straight into the item buffer (then a build follows)."""
+        import torch
+
+        view = self.items[:self.cap * self.item_len].view(self.cap, self.item_len)
+        if self.pending:
+            idx = sorted(self.pending)
+            vals = np.stack([self.pending[i] for i in idx])
+            view[torch.tensor(idx, dtype=torch.int64, device=self.device)] = torch.from_numpy(vals).to(self.device)
+        if self.appended:
+            view[self.n:self.n + len(self.appended)] = torch.from_numpy(np.stack(self.appended)).to(self.device)
+        self.n += len(self.appended)
+        self.pending, self.appended = {}, []
+
+    def flush(self, container_off: int):
+        """This tree's entry of the next trees_update.  A list that outgrew its
+        capacity (doubled, moved) or is dirty enough for its host handle to
+        rebuild goes through the build entry and enters with nothing dirty."""
+        import torch
+
+        from . import device as D
+
+        n_new, dirty = len(self), len(self.pending) + len(self.appended)
+        if n_new > self.cap:
+            old, n = self.items, self.n
+            self._alloc(max(2 * self.cap, n_new))
+            self.items[:n * self.item_len].copy_(old[:n * self.item_len])
+            self._write_through()
+            self._build()
+        elif dirty and n_new // _REBUILD_DIV[self.kind] <= dirty:
+            self._write_through()
+            self._build()
+        idx = vals = None
+        k = len(self.pending)
+        if self.pending or self.appended:
+            order = sorted(self.pending)
+            rows = [self.pending[i] for i in order] + self.appended
+            vals = torch.from_numpy(np.stack(rows).reshape(-1)).to(self.device)
+            if k:
+                idx = torch.tensor(order, dtype=torch.int64, device=self.device)
+        t = D.TreeArgs(self.kind, self.items, self.n, len(self), self.cap, self.item_len, self.levels, self.root,
+                       level0=self.level0, idx=idx, k_idx=k, values=vals, spec=self.spec, container_off=container_off)
+        self.n = len(self)
+        self.pending, self.appended = {}, []
+        return t
+
+
+class ResidentBeaconState:
+    """A whole ``BeaconState`` kept in HBM: the ten lists as
+    resident trees (registry, crosslinks, attestations and votes as struct
+    trees, the balances as list trees, the four root arrays as bytes trees),
+    the 536-B hash message of the state struct beside them.  Changes are
+    collected on the host; ``root()`` is ONE ``device.trees_update`` over the
+    ten trees -- every climb and the state hash in one launch -- and one 32-B
+    read-back.  Everything runs on torch's current stream of ``device``.
+
+    Values are packed rows: ``VALIDATOR_DTYPE`` records, u64 balances, (k, 32)
+    roots, ``pack_crosslinks`` / ``pack_eth1_votes`` records; attestations go
+    in as an ``Attestations``."""
+
+    def __init__(self, device="cuda"):
+        import torch
+
+        self.device = torch.device(device)
+        self.trees = {attr: _ResidentTree(kind, item_len, spec, self.device)
+                      for attr, _, kind, item_len, spec in RESIDENT_TREES}
+        self._off = {attr: CONTAINER_OFF[field_name] for attr, field_name, _, _, _ in RESIDENT_TREES}
+        self.container = torch.zeros(CONTAINER_LEN + 8, dtype=torch.uint8, device=self.device)
+        self.state_root = torch.zeros(32, dtype=torch.uint8, device=self.device)
+        self._ws = None
+        self._att_cap = 48
+
+    # ---- the small fields: written into the message when they are set
+    def _put(self, off: int, data: bytes) -> None:
+        import torch
+
+        self.container[off:off + len(data)].copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
+
+    def set_scalar(self, name: str, value: int) -> None:
+        if name not in _SCALARS:
+            raise KeyError(name)
+        self._put(CONTAINER_OFF[name], _st.pack("<Q", int(value)))
+
+    def set_seeds(self, previous: bytes, current: bytes) -> None:
+        msgs = np.empty((2, 36), dtype=np.uint8)
+        msgs[:, :4] = np.frombuffer(_st.pack("<I", 32), dtype=np.uint8)
+        msgs[0, 4:] = np.frombuffer(bytes(previous), dtype=np.uint8)
+        msgs[1, 4:] = np.frombuffer(bytes(current), dtype=np.uint8)
+        h = hash_batch(msgs, 36)
+        self._put(CONTAINER_OFF["PreviousEpochSeedHash32"], bytes(h[0]) + bytes(h[1]))
+
+    def set_eth1_data(self, eth1_data) -> None:
+        rec = np.ascontiguousarray(eth1_data, dtype=np.uint8).reshape(1, 64)
+        self._put(CONTAINER_OFF["LatestEth1Data"], bytes(struct_roots_packed(rec, ETH1_DATA_FIELDS)[0]))
+
+    def set_fork(self, fork) -> None:
+        msg = b"".join(_st.pack("<Q", int(x)) for x in fork)
+        self._put(CONTAINER_OFF["Fork"], hash_batch_var([msg])[0])
+
+    # ---- the lists
+    def _att_rows(self, att: "Attestations") -> np.ndarray:
+        """``att`` packed for the attestation tree; bitfields longer than its
+        slots widen the layout: the resident records are repacked and the tree
+        rebuilt."""
+        longest = max([len(x) for x in att.aggregation_bitfield] + [len(x) for x in att.custody_bitfield] + [0])
+        t = self.trees["attestations"]
+        if longest > self._att_cap:
+            new_cap = max(2 * self._att_cap, (longest + 3) & ~3)
+            rows = np.zeros((t.n, t.item_len), np.uint8)
+            if t.n:  # the resident records with their pending changes, then the pending appends
+                rows = t.items[:t.n * t.item_len].cpu().numpy().reshape(t.n, t.item_len).copy()
+            for i, row in t.pending.items():
+                rows[i] = row
+            rows = np.concatenate([rows] + [r.reshape(1, -1) for r in t.appended])
+            rows = widen_attestation_records(rows, self._att_cap, new_cap)
+            self._att_cap = new_cap
+            t.item_len, t.spec = pending_attestation_record_len(new_cap), pending_attestation_fields(new_cap)
+            t.items = None  # another record length: new buffers
+            t.replace(rows)
+        return pack_attestations(att, self._att_cap)[0]
+
+    def _rows(self, name: str, values):
+        if name == "attestations" and isinstance(values, Attestations):
+            return self._att_rows(values)
+        return values
+
+    def assign(self, state: BeaconState) -> None:
+        """Every tree built from ``state`` (the build entry points), every small field set."""
+        for name in _SCALARS:
+            self.set_scalar(name, state.scalars[name])
+        self.set_seeds(bytes(state.seeds[0]), bytes(state.seeds[1]))
+        self.set_eth1_data(state.eth1_data)
+        self.set_fork(state.fork)
+        self.replace("registry", state.registry.records)
+        self.replace("balances", state.balances.astype("<u8"))
+        self.replace("randao_mixes", state.randao_mixes)
+        self.replace("crosslinks", pack_crosslinks(state.crosslink_epochs, state.crosslink_roots))
+        self.replace("latest_block_roots", state.latest_block_roots)
+        self.replace("batched_block_roots", state.batched_block_roots)
+        self.replace("penalized_balances", state.penalized_balances.astype("<u8"))
+        self.replace("attestations", state.attestations)
+        self.replace("index_roots", state.index_roots)
+        self.replace("eth1_votes", pack_eth1_votes(state.eth1_votes, state.eth1_vote_counts))
+
+    def count(self, name: str) -> int:
+        """Items of list ``name``, pending appends included."""
+        return len(self.trees[name])
+
+    def update(self, name: str, indices, values) -> None:
+        """list[indices[j]] = values[j] in order (of a repeated index the last
+        value wins); an index >= len raises and changes nothing."""
+        t = self.trees[name]
+        for i in np.asarray(indices).reshape(-1):  # before anything changes (packing may widen the attestation slots)
+            if int(i) < 0 or int(i) >= len(t):
+                raise IndexError(f"{name}: index {int(i)} beyond {len(t)} items")
+        t.update(indices, self._rows(name, values))
+
+    def append(self, name: str, values) -> None:
+        """Append; past the capacity the list doubles it and is rebuilt."""
+        rows = self._rows(name, values)
+        self.trees[name].append(rows)
+
+    def replace(self, name: str, values) -> None:
+        """Any new content for a list, a shorter one included, through the build entry."""
+        if name == "attestations" and isinstance(values, Attestations):
+            t = self.trees[name]
+            t.n, t.pending, t.appended = 0, {}, []  # nothing to carry over should the slots widen
+            values = self._att_rows(values)
+        self.trees[name].replace(values)
+
+    def root(self) -> bytes:
+        """The state root: one trees_update over the ten trees (a rebuilt tree
+        enters with nothing dirty, so its root still reaches the message), one
+        32-B read-back."""
+        import torch
+
+        from . import device as D
+
+        with torch.cuda.device(self.device):
+            trees = [self.trees[attr].flush(self._off[attr]) for attr, *_ in RESIDENT_TREES]
+            need = D.trees_update_workspace_bytes(trees)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            D.trees_update(trees, self.container, CONTAINER_LEN, self.state_root, self._ws)
+            return bytes(self.state_root.cpu().numpy())
