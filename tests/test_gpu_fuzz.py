@@ -4,7 +4,9 @@ merkleHash at random sizes, item lengths and byte offsets (every planner
 branch: spread leaf passes, lane-pair passes, fused throughput passes),
 many lists per call, struct roots of random layouts (both struct kernels
 and the generic one), deposit tries grown by random batches with the
-per-log check, and MerkleRoot.  Sizes keep the oracle to seconds."""
+per-log check, and MerkleRoot.  Sizes keep the oracle to seconds.
+_item_len and _layout are shared with the resident-tree fuzz
+(tests/tree_fuzz_plan.py, test_gpu_tree_fuzz.py)."""
 import os
 import random
 

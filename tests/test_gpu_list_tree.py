@@ -2,7 +2,10 @@
 the root and EVERY stored node of every level against a restatement of the
 definition (include/prysm_merkle.h) over the oracle's
 Keccak, after builds, in-place updates, appends, a random sequence, two trees
-on two streams and a replayed hipGraph."""
+on two streams and a replayed hipGraph.  oracle_tree, split_levels /
+device_levels and compare_tree / check_tree live here and are shared with
+test_gpu_trees_update.py, test_gpu_tree_fuzz.py and test_tree_fuzz_host.py
+(compare_tree is check_tree's comparison over host arrays)."""
 import ctypes
 
 import numpy as np
@@ -64,8 +67,8 @@ def oracle_tree(buf, n, L):
     return levels, root
 
 
-def device_levels(lv, n, cap, L):
-    host = lv.cpu().numpy()
+def split_levels(host, n, cap, L):
+    """The stored nodes of every level of a level array held in a host array."""
     out, off, capd, c = [], 0, _chunks(cap, L), _chunks(n, L)
     while c > 1:
         capd, c = (capd + 1) // 2, (c + 1) // 2
@@ -74,20 +77,30 @@ def device_levels(lv, n, cap, L):
     return out
 
 
+def device_levels(lv, n, cap, L):
+    return split_levels(lv.cpu().numpy(), n, cap, L)
+
+
+def compare_tree(items, got, root, want_buf, n, L, what):
+    """Host arrays (the item buffer, split_levels' levels, the root) against a
+    fresh oracle build: the comparison of check_tree, without a device."""
+    assert np.array_equal(items[:n * L], want_buf[:n * L]), f"{what}: items"
+    levels, want_root = oracle_tree(want_buf, n, L)
+    assert bytes(root) == want_root, f"{what}: root"
+    assert len(got) == len(levels)
+    for d, (g, w) in enumerate(zip(got, levels), 1):
+        bad = np.flatnonzero((g != w).any(axis=1))
+        assert bad.size == 0, f"{what}: level {d} nodes {bad[:8]} of {len(w)}"
+
+
 def check_tree(tree, want_buf, what):
     """Item buffer, every level and the root against a fresh oracle build."""
     import torch
 
     torch.cuda.synchronize()
     n, L = tree.n, tree.L
-    assert np.array_equal(tree.items[:n * L].cpu().numpy(), want_buf[:n * L]), f"{what}: items"
-    levels, root = oracle_tree(want_buf, n, L)
-    assert bytes(tree.root.cpu().numpy()) == root, f"{what}: root"
-    got = device_levels(tree.lv, n, tree.cap, L)
-    assert len(got) == len(levels)
-    for d, (g, w) in enumerate(zip(got, levels), 1):
-        bad = np.flatnonzero((g != w).any(axis=1))
-        assert bad.size == 0, f"{what}: level {d} nodes {bad[:8]} of {len(w)}"
+    compare_tree(tree.items[:n * L].cpu().numpy(), device_levels(tree.lv, n, tree.cap, L),
+                 tree.root.cpu().numpy(), want_buf, n, L, what)
 
 
 class Tree:

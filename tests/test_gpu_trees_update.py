@@ -6,7 +6,9 @@ mk_dev_ssz_*_tree_update; the item buffer, level 0, every stored level and the
 root must be equal byte for byte, and level 0 and the root must equal the
 oracle's (O.merkle_hash_flat over the items, over O.struct_roots /
 oracle/ssz_ref.tree_hash of every record, over O.elem_digests).  Then the
-container hash, back-to-back calls, two streams and a replayed hipGraph."""
+container hash, back-to-back calls, two streams and a replayed hipGraph.
+(device_levels is test_gpu_list_tree.py's; random lives of mixed trees and
+the container at every length class are in test_gpu_tree_fuzz.py.)"""
 import numpy as np
 import pytest
 
