@@ -700,6 +700,35 @@ int mk_dev_deposit_trie_levels(mk_call* call, void* d_levels, uint64_t capacity,
 int mk_dev_deposit_trie_branch(mk_call* call, const void* d_levels, uint64_t capacity, uint64_t count,
                                uint32_t depth, uint64_t index, void* d_branch, void* stream);
 
+/* GenerateMerkleBranch for k indices and Root(), as of a past deposit count:
+ * what the reference's trie answered right after its as_of-th
+ * UpdateDepositTrie (0 <= as_of <= count), from the level array later appends
+ * left behind.  verifyDeposit (core/blocks/block_operations.go:624-641) checks
+ * a deposit against state.LatestEth1Data.DepositRootHash32, an earlier state
+ * of the trie than the one powchain holds; these are the branches for it.
+ * d_indices: k indices on the device, any order, repeats allowed, none read
+ * on the host (a sibling that did not exist at as_of, or that no index below
+ * 2^depth can have, is 0^32).  d_branches: k x depth x 32 bytes, branch j at
+ * 32 * depth * j.  d_root_at (nullable): the 32-B root as of as_of (0^32 for
+ * as_of == 0).  One launch; allocates nothing, uploads nothing and never
+ * synchronizes, so it can be captured into a hipGraph.  d_levels, d_branches
+ * and d_root_at 16-B aligned.  MK_EINVAL (nothing launched): as_of > count,
+ * count > capacity, depth outside 1..63.  k == 0 writes only d_root_at. */
+int mk_dev_deposit_trie_branches(mk_call* call, const void* d_levels, uint64_t capacity, uint64_t count,
+                                 uint32_t depth, uint64_t as_of, const uint64_t* d_indices, uint64_t k,
+                                 void* d_branches, void* d_root_at, void* stream);
+/* verifyDeposit for a batch of n deposits: ok[i] = fold(Hash(data[offs[i],
+ * offs[i+1])), branches[i*depth..], indices[i] + 2^tree_depth) == root, with
+ * root = d_roots[0, 32) for every deposit when root_stride == 0 (a block's
+ * deposits against the state's deposit root) or d_roots[32 i, 32 i + 32) when
+ * root_stride == 32; any other root_stride is MK_EINVAL.  Replaces a
+ * mk_dev_hash_batch_var call plus the leaf-hash verifier.  d_offs: n + 1
+ * offsets into d_data, device.  d_branches and d_roots 16-B aligned.  One
+ * launch; allocates nothing, uploads nothing, never synchronizes. */
+int mk_dev_verify_deposits(mk_call* call, const void* d_data, const uint64_t* d_offs, const void* d_branches,
+                           const uint64_t* d_indices, uint64_t n, uint32_t depth, uint32_t tree_depth,
+                           const void* d_roots, uint32_t root_stride, void* d_ok, void* stream);
+
 /* Device-resident trie handle: the Go DepositTrie (deposit_trie.go:13-16)
  * holds one.  Levels stay in HBM (capacity doubles on demand); appends
  * recompute only the right edge, so powchain's read-Root-then-Update loop
@@ -724,6 +753,15 @@ int mk_deposit_trie_save_logs(mk_call* call, mk_trie* t, const uint8_t* data, co
 int mk_deposit_trie_root(mk_call* call, mk_trie* t, uint8_t root[32]);
 /* depth x 32 bytes: GenerateMerkleBranch(index). */
 int mk_deposit_trie_branch(mk_call* call, mk_trie* t, uint64_t index, uint8_t* branch);
+/* k x depth x 32 bytes: GenerateMerkleBranch(indices[j]) as of as_of <=
+ * count deposits (mk_dev_deposit_trie_branches over the handle: host indices
+ * and output, the root as of as_of to root_at when it is not NULL).
+ * as_of > count: MK_EINVAL, nothing written.  k == 0 writes only root_at.  A
+ * very large k runs in chunks of bounded device scratch. */
+int mk_deposit_trie_branches(mk_call* call, mk_trie* t, uint64_t as_of, const uint64_t* indices, uint64_t k,
+                             uint8_t* branches, uint8_t* root_at);
+/* Root() as of as_of <= count deposits (0^32 for as_of == 0). */
+int mk_deposit_trie_root_at(mk_call* call, mk_trie* t, uint64_t as_of, uint8_t root[32]);
 /* Leaf hashes [first, first + cnt) (Hash(deposit)), cnt x 32 bytes. */
 int mk_deposit_trie_leaves(mk_call* call, mk_trie* t, uint64_t first, uint64_t cnt, uint8_t* out);
 
@@ -732,6 +770,11 @@ int mk_deposit_trie_leaves(mk_call* call, mk_trie* t, uint64_t first, uint64_t c
 int mk_verify_merkle_branches(mk_call* call, const uint8_t* leaves, const uint8_t* branches,
                               const uint64_t* indices, uint64_t n, uint32_t depth, uint32_t tree_depth,
                               const uint8_t* roots, uint8_t* ok);
+/* mk_dev_verify_deposits over host buffers (deposit i = data[offs[i],
+ * offs[i+1]); roots: 32 bytes for root_stride == 0, n x 32 for 32). */
+int mk_verify_deposits(mk_call* call, const uint8_t* data, const uint64_t* offs, const uint8_t* branches,
+                       const uint64_t* indices, uint64_t n, uint32_t depth, uint32_t tree_depth,
+                       const uint8_t* roots, uint32_t root_stride, uint8_t* ok);
 
 /* ---- synthetic inputs (bench / tests) ----------------------------------- */
 /* Bytes [8*word0, 8*word0 + nbytes) of the SplitMix64 stream;

@@ -111,6 +111,11 @@ _SIGS = {
     "mk_deposit_trie_root": (_int, [_cp, _vp, _vp]),
     "mk_deposit_trie_branch": (_int, [_cp, _vp, _u64, _vp]),
     "mk_deposit_trie_leaves": (_int, [_cp, _vp, _u64, _u64, _vp]),
+    "mk_dev_deposit_trie_branches": (_int, [_cp, _vp, _u64, _u64, _u32, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "mk_deposit_trie_branches": (_int, [_cp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "mk_deposit_trie_root_at": (_int, [_cp, _vp, _u64, _vp]),
+    "mk_dev_verify_deposits": (_int, [_cp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "mk_verify_deposits": (_int, [_cp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32, _vp]),
     "mk_ssz_list_tree_levels_bytes": (_u64, [_u64, _u32]),
     "mk_ssz_list_tree_build_workspace_bytes": (_u64, [_u64, _u32]),
     "mk_dev_ssz_list_tree_build": (_int, [_cp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),

@@ -4118,6 +4118,142 @@ __global__ void k_trie_branch(const uint4* __restrict__ levels, uint64_t cap, ui
     branch[2 * d + 1] = v1;
 }
 
+// GenerateMerkleBranch for k indices, and Root(), AS OF a past deposit count
+// c = as_of <= count: what the reference's trie answered right after its c-th
+// UpdateDepositTrie (deposit_trie.go:29-63), from the level array the later
+// appends left behind.  The trie is append-only, so a node whose leaves all
+// lie below c still holds its value of that moment, a node whose leaves all
+// lie at or above c did not exist (0^32, the map miss), and per level only the
+// ancestor of leaf c - 1 can straddle c.  Those straddling nodes E_d are one
+// dependent chain: with p = (c - 1) >> d, E_{d+1} = K(level_d[p - 1] || E_d)
+// for odd p, else K(E_d || 0^32).  Level d straddles iff 2^d does not divide c
+// (and count > c), so the chain starts from the stored node of level
+// d0 - 1 = ctz(c) and is empty when c == count.
+// Every workgroup runs the chain itself, on wave 0 in spread form with the left
+// siblings prefetched into LDS (the walk of k_trie_prefix_roots), so nothing
+// is handed from one workgroup to another; then each wave writes one branch
+// per turn as one contiguous block: lane pair (2d, 2d + 1) takes the two 16-B
+// halves of level d's sibling s = (index >> d) ^ 1, which is 0^32 for s > p,
+// E_d for s == p on a straddling level, the stored node otherwise.
+__global__ __launch_bounds__(64 * kBranchWaves) void k_trie_branches_at(
+    const uint4* __restrict__ levels, uint64_t cap, uint64_t count, uint64_t as_of, uint32_t depth,
+    const uint64_t* __restrict__ indices, uint64_t k, uint4* __restrict__ branches, uint4* __restrict__ root_at) {
+    __shared__ uint4 sib[64][2];    // chain: level d's left sibling
+    __shared__ uint4 edge[64][2];   // E_d for d0 <= d <= depth
+    __shared__ uint64_t lvoff[64];  // first node of level d in the level array
+    const uint32_t w = threadIdx.x >> 6, L = threadIdx.x & 63u;
+    const uint64_t c = as_of, last = c - 1;
+    const bool chain = c != 0 && count > c && (uint32_t)__ffsll((long long)c) <= depth;  // block-uniform
+    const uint32_t d0 = chain ? (uint32_t)__ffsll((long long)c) : 64u;  // lowest straddling level
+    if (L <= depth && (w == 0 ? chain : w == 1)) {
+        uint64_t off = 0, capd = cap;
+        for (uint32_t d = 0; d < L; ++d) {
+            off += capd;
+            capd = (capd + 1) / 2;
+        }
+        if (w == 1) {
+            lvoff[L] = off;
+        } else if (L + 1 >= d0 && L < depth && ((last >> L) & 1u)) {
+            const uint64_t node = off + (last >> L) - 1;
+            sib[L][0] = levels[2 * node];
+            sib[L][1] = levels[2 * node + 1];
+        }
+    }
+    __syncthreads();
+    if (w == 0 && chain) {
+        const spread::LaneLH cst = spread::lane_consts_lh(L);
+        const uint32_t ci = cst.i;
+        uint32_t plo = 0u, phi = 0u;  // the path node's word ci on lanes ci < 4
+        if (ci < 4u) {
+            const uint2 v = reinterpret_cast<const uint2*>(levels)[4 * (lvoff[d0 - 1] + (last >> (d0 - 1))) + ci];
+            plo = v.x;
+            phi = v.y;
+        }
+        for (uint32_t d = d0 - 1; d < depth; ++d) {
+            const bool right = ((last >> d) & 1u) != 0;  // wave-uniform
+            // path words moved to Keccak lanes 4..7 (GPU lanes 0..3 hold 0..3)
+            const uint32_t src = 4u * ((ci - 4u) & 3u);
+            const uint32_t mlo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)plo);
+            const uint32_t mhi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)phi);
+            uint32_t lo = 0u, hi = 0u;
+            if (ci < 4u) {
+                if (right) {
+                    const uint4 h = sib[d][ci >> 1];
+                    lo = (ci & 1u) ? h.z : h.x;
+                    hi = (ci & 1u) ? h.w : h.y;
+                } else {
+                    lo = plo;
+                    hi = phi;
+                }
+            } else if (ci < 8u && right) {
+                lo = mlo;
+                hi = mhi;
+            } else if (ci == 8u) {
+                lo = 1u;
+            }
+            if (ci == 16u) hi = 0x80000000u;
+            spread::keccak_f_lh(lo, hi, cst);
+            plo = lo;
+            phi = hi;
+            if (L < 4u) reinterpret_cast<uint2*>(&edge[d + 1][0])[L] = make_uint2(lo, hi);
+        }
+    }
+    __syncthreads();
+    if (root_at && blockIdx.x == 0 && threadIdx.x < 2u) {  // E_depth; the stored root when no level straddles
+        uint4 r = make_uint4(0, 0, 0, 0);
+        if (chain)
+            r = edge[depth][threadIdx.x];
+        else if (c != 0)
+            r = levels[2 * lvoff[depth] + threadIdx.x];
+        root_at[threadIdx.x] = r;
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * kBranchWaves;
+    for (uint64_t g = (uint64_t)blockIdx.x * kBranchWaves + w; g < k; g += stride) {
+        const uint64_t index = indices[g];
+        for (uint32_t q = L; q < 2 * depth; q += 64) {
+            const uint32_t d = q >> 1, h = q & 1u;
+            const uint64_t s = (index >> d) ^ 1ull, p = last >> d;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (c != 0 && s <= p) v = (s == p && d >= d0) ? edge[d][h] : levels[2 * (lvoff[d] + s) + h];
+            branches[2 * (uint64_t)depth * g + q] = v;
+        }
+    }
+}
+
+// verifyDeposit for a batch (core/blocks/block_operations.go:624-641): thread
+// i hashes deposit data i = data[offs[i], offs[i+1]) into its leaf (the sponge
+// of k_keccak_var), folds its `depth` siblings into it (the fold of
+// k_verify_branches) and compares with the batch's one root (root_stride == 0:
+// a block's deposits against the state's deposit root) or with root i
+// (root_stride == 32).
+__global__ __launch_bounds__(256) void k_verify_deposits(const uint8_t* __restrict__ data,
+                                                         const uint64_t* __restrict__ offs,
+                                                         const uint4* __restrict__ branches,
+                                                         const uint64_t* __restrict__ indices, uint32_t depth,
+                                                         uint32_t tree_depth, const uint4* __restrict__ roots,
+                                                         uint32_t root_stride, uint64_t n,
+                                                         uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t a = offs[i], b = offs[i + 1];
+    uint4 v0, v1;
+    sponge_generic(data + a, b - a, 0, false, 0, v0, v1);
+    uint64_t idx = indices[i] + (tree_depth >= 64 ? 0ull : (1ull << tree_depth));
+    const uint4* br = branches + 2 * (uint64_t)depth * i;
+    for (uint32_t d = 0; d < depth; ++d) {
+        const uint4 b0 = br[2 * d], b1 = br[2 * d + 1];
+        if (idx & 1)
+            hash_pair(b0, b1, v0, v1, false, v0, v1);
+        else
+            hash_pair(v0, v1, b0, b1, false, v0, v1);
+        idx >>= 1;
+    }
+    const uint4* rt = roots + (root_stride ? 2 * i : 0);
+    const uint4 r0 = rt[0], r1 = rt[1];
+    ok[i] = (v0.x == r0.x && v0.y == r0.y && v0.z == r0.z && v0.w == r0.w && v1.x == r1.x && v1.y == r1.y &&
+             v1.z == r1.z && v1.w == r1.w);
+}
+
 // ----------------------------------------------------------------------------
 // Many lists (segmented merkleHash, hash.go:194-239 per list): one launch per
 // level for all lists with nodes at that level.  Thread t of the launch maps

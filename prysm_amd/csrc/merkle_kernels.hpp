@@ -163,6 +163,14 @@ __global__ void k_trie_prefix_roots(const uint4* levels, uint64_t cap, uint64_t 
                                     uint4* roots);
 __global__ void k_trie_branch(const uint4* levels, uint64_t cap, uint64_t count, uint32_t depth, uint64_t index,
                               uint4* branch);
+// branches of k indices (and the root) as of a past deposit count; one branch per wave, kBranchWaves per workgroup
+constexpr uint32_t kBranchWaves = 4;
+__global__ void k_trie_branches_at(const uint4* levels, uint64_t cap, uint64_t count, uint64_t as_of, uint32_t depth,
+                                   const uint64_t* indices, uint64_t k, uint4* branches, uint4* root_at);
+// verifyDeposit for a batch: leaf hash of the deposit data, the fold, the compare (root_stride 0: one shared root)
+__global__ void k_verify_deposits(const uint8_t* data, const uint64_t* offs, const uint4* branches,
+                                  const uint64_t* indices, uint32_t depth, uint32_t tree_depth, const uint4* roots,
+                                  uint32_t root_stride, uint64_t n, uint8_t* ok);
 template <bool LEAF>
 __global__ void k_many_level(const uint8_t* items, const ManyList* lists, const ManyAct* act, uint32_t nact,
                              uint64_t nodes, const uint4* in, uint4* out, uint4* tops);

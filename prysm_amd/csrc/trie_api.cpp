@@ -379,6 +379,42 @@ int dev_trie_branch(const void* d_levels, uint64_t cap, uint64_t count, uint32_t
     return launched();
 }
 
+// Branches of k indices and the root as of `as_of` <= count deposits, one
+// launch: every workgroup walks the straddling chain itself, then its waves
+// take one branch per turn (k_trie_branches_at).
+constexpr uint64_t kBranchGridMax = 2048;  // workgroups: 8 per CU, the rest by grid stride
+int dev_trie_branches_at(const void* d_levels, uint64_t cap, uint64_t count, uint32_t depth, uint64_t as_of,
+                         const uint64_t* d_indices, uint64_t k, void* d_branches, void* d_root_at, hipStream_t st) {
+    if (depth == 0 || depth > 63) return fail(MK_EINVAL, "depth %u out of range (1..63)", depth);
+    if (count > cap) return fail(MK_EINVAL, "count > capacity");
+    if (as_of > count)
+        return fail(MK_EINVAL, "as_of %llu beyond %llu deposits", (unsigned long long)as_of, (unsigned long long)count);
+    if ((as_of && !d_levels) || (k && (!d_indices || !d_branches))) return fail(MK_EINVAL, "null pointer");
+    if (((uintptr_t)d_levels | (uintptr_t)d_branches | (uintptr_t)d_root_at) % 16 || (uintptr_t)d_indices % 8)
+        return fail(MK_EINVAL, "levels, branches and root_at need 16-B alignment, indices 8-B");
+    if (k > UINT64_MAX / (32ull * depth)) return fail(MK_EINVAL, "k x depth x 32 bytes overflow");
+    if (k == 0 && !d_root_at) return MK_OK;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(k, mk::kBranchWaves), kBranchGridMax));
+    hipLaunchKernelGGL(mk::k_trie_branches_at, dim3(grid), dim3(64 * mk::kBranchWaves), 0, st, (const uint4*)d_levels,
+                       cap, count, as_of, depth, d_indices, k, (uint4*)d_branches, (uint4*)d_root_at);
+    return launched();
+}
+
+int dev_verify_deposits(const void* d_data, const uint64_t* d_offs, const void* d_branches, const uint64_t* d_indices,
+                        uint64_t n, uint32_t depth, uint32_t tree_depth, const void* d_roots, uint32_t root_stride,
+                        void* d_ok, hipStream_t st) {
+    if (root_stride != 0 && root_stride != 32)
+        return fail(MK_EINVAL, "root_stride %u (0: one root for the batch, 32: one per deposit)", root_stride);
+    if (n == 0) return MK_OK;
+    if (!d_offs || !d_indices || !d_roots || !d_ok || (depth && !d_branches)) return fail(MK_EINVAL, "null pointer");
+    if (((uintptr_t)d_branches | (uintptr_t)d_roots) % 16 || ((uintptr_t)d_offs | (uintptr_t)d_indices) % 8)
+        return fail(MK_EINVAL, "branches and roots need 16-B alignment, offsets and indices 8-B");
+    hipLaunchKernelGGL(mk::k_verify_deposits, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const uint8_t*)d_data, d_offs,
+                       (const uint4*)d_branches, d_indices, depth, tree_depth, (const uint4*)d_roots, root_stride, n,
+                       (uint8_t*)d_ok);
+    return launched();
+}
+
 int host_merkle_root(const uint8_t* data, const uint64_t* offs, uint64_t n, uint8_t* leaves_out,
                      uint8_t* out) {
     if (!out || (n && !offs)) return fail(MK_EINVAL, "null pointer");
@@ -582,6 +618,46 @@ int trie_branch(mk_trie* t, uint64_t index, uint8_t* branch) {
     return MK_OK;
 }
 
+// Branches of k indices (and the root) as of `as_of` deposits.  The handle's
+// scratch holds [root 32 B | chunk indices | chunk branches]; a chunk is at
+// most kBranchChunk indices (8.3 MB of scratch at depth 32), one launch, one
+// read-back and one synchronize each.
+constexpr uint64_t kBranchChunk = 8192;
+int trie_branches(mk_trie* t, uint64_t as_of, const uint64_t* indices, uint64_t k, uint8_t* branches,
+                  uint8_t* root_at) {
+    if (!t || (k && (!indices || !branches))) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    if (as_of > t->count)
+        return fail(MK_EINVAL, "as_of %llu beyond %llu deposits", (unsigned long long)as_of,
+                    (unsigned long long)t->count);
+    const size_t bb = 32 * (size_t)t->depth;  // one branch
+    if (k > SIZE_MAX / bb) return fail(MK_EINVAL, "k x depth x 32 bytes overflow");
+    if (as_of == 0) {  // no node existed yet: every sibling and the root read 0^32
+        if (k) std::memset(branches, 0, bb * k);
+        if (root_at) std::memset(root_at, 0, 32);
+        return MK_OK;
+    }
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    const uint64_t m_max = std::min(k, kBranchChunk);
+    const size_t idx_off = 32, br_off = idx_off + ((8 * m_max + 15) & ~(size_t)15);
+    TRY(grow(t->branch, br_off + bb * m_max));
+    uint8_t* base = (uint8_t*)t->branch.p;
+    uint64_t pos = 0;
+    do {
+        const uint64_t m = std::min(k - pos, kBranchChunk);
+        void* d_root = (pos == 0 && root_at) ? base : nullptr;
+        if (m) HIPCHK(hipMemcpyAsync(base + idx_off, indices + pos, 8 * m, hipMemcpyHostToDevice, st));
+        TRY(dev_trie_branches_at(t->levels.p, t->cap, t->count, t->depth, as_of, (const uint64_t*)(base + idx_off), m,
+                                 base + br_off, d_root, st));
+        if (m) HIPCHK(hipMemcpyAsync(branches + bb * pos, base + br_off, bb * m, hipMemcpyDeviceToHost, st));
+        if (d_root) HIPCHK(hipMemcpyAsync(root_at, base, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        pos += m;
+    } while (pos < k);
+    return MK_OK;
+}
+
 int trie_leaves(mk_trie* t, uint64_t first, uint64_t cnt, uint8_t* out) {
     if (!t || (cnt && !out)) return fail(MK_EINVAL, "null pointer");
     std::lock_guard<std::mutex> tl(t->mu);
@@ -622,6 +698,41 @@ int host_verify(const uint8_t* leaves, const uint8_t* branches, const uint64_t* 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(ok, c->out.p, n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return MK_OK;
+}
+
+int host_verify_deposits(const uint8_t* data, const uint64_t* offs, const uint8_t* branches, const uint64_t* indices,
+                         uint64_t n, uint32_t depth, uint32_t tree_depth, const uint8_t* roots, uint32_t root_stride,
+                         uint8_t* ok) {
+    if (root_stride != 0 && root_stride != 32)
+        return fail(MK_EINVAL, "root_stride %u (0: one root for the batch, 32: one per deposit)", root_stride);
+    if (n && (!offs || !indices || !roots || !ok || (depth && !branches))) return fail(MK_EINVAL, "null pointer");
+    if (n && offs[n] > offs[0] && !data) return fail(MK_EINVAL, "null deposit data");
+    TRY(bind_call());
+    if (n == 0) return MK_OK;
+    DevCtx* c = ctx();
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = c->stream;
+    const size_t inb = offs[n] - offs[0], bb = 32 * (size_t)depth * n, rb = root_stride ? 32 * n : 32;
+    // in: [roots | branches | data], aux: [offsets (n + 1) | indices (n)]
+    TRY(grow(c->in, rb + bb + inb + 16));
+    TRY(grow(c->aux, 8 * (2 * n + 1)));
+    TRY(grow(c->out, n));
+    uint8_t* d_roots = (uint8_t*)c->in.p;
+    uint8_t* d_br = d_roots + rb;
+    uint8_t* d_data = d_br + bb;
+    uint64_t* d_offs = (uint64_t*)c->aux.p;
+    uint64_t* d_idx = d_offs + n + 1;
+    std::vector<uint64_t> rel(offs, offs + n + 1);
+    for (auto& o : rel) o -= offs[0];
+    HIPCHK(hipMemcpyAsync(d_roots, roots, rb, hipMemcpyHostToDevice, st));
+    if (bb) HIPCHK(hipMemcpyAsync(d_br, branches, bb, hipMemcpyHostToDevice, st));
+    if (inb) HIPCHK(hipMemcpyAsync(d_data, data + offs[0], inb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_offs, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_idx, indices, 8 * n, hipMemcpyHostToDevice, st));
+    TRY(dev_verify_deposits(d_data, d_offs, d_br, d_idx, n, depth, tree_depth, d_roots, root_stride, c->out.p, st));
+    HIPCHK(hipMemcpyAsync(ok, c->out.p, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // `rel` and the caller's buffers are released after this
     return MK_OK;
 }
 
@@ -790,6 +901,43 @@ int mk_deposit_trie_save_logs(mk_call* call, mk_trie* t, const uint8_t* data, co
 int mk_deposit_trie_branch(mk_call* call, mk_trie* t, uint64_t index, uint8_t* branch) {
     Scope S(call);
     return S.done(trie_branch(t, index, branch));
+}
+
+int mk_dev_deposit_trie_branches(mk_call* call, const void* d_levels, uint64_t capacity, uint64_t count,
+                                 uint32_t depth, uint64_t as_of, const uint64_t* d_indices, uint64_t k,
+                                 void* d_branches, void* d_root_at, void* stream) {
+    return dev_entry(call, stream, [&]() -> int {
+        return dev_trie_branches_at(d_levels, capacity, count, depth, as_of, d_indices, k, d_branches, d_root_at,
+                                    (hipStream_t)stream);
+    });
+}
+
+int mk_deposit_trie_branches(mk_call* call, mk_trie* t, uint64_t as_of, const uint64_t* indices, uint64_t k,
+                             uint8_t* branches, uint8_t* root_at) {
+    Scope S(call);
+    return S.done(trie_branches(t, as_of, indices, k, branches, root_at));
+}
+
+int mk_deposit_trie_root_at(mk_call* call, mk_trie* t, uint64_t as_of, uint8_t root[32]) {
+    Scope S(call);
+    if (!root) return S.done(fail(MK_EINVAL, "null pointer"));
+    return S.done(trie_branches(t, as_of, nullptr, 0, nullptr, root));
+}
+
+int mk_dev_verify_deposits(mk_call* call, const void* d_data, const uint64_t* d_offs, const void* d_branches,
+                           const uint64_t* d_indices, uint64_t n, uint32_t depth, uint32_t tree_depth,
+                           const void* d_roots, uint32_t root_stride, void* d_ok, void* stream) {
+    return dev_entry(call, stream, [&]() -> int {
+        return dev_verify_deposits(d_data, d_offs, d_branches, d_indices, n, depth, tree_depth, d_roots, root_stride,
+                                   d_ok, (hipStream_t)stream);
+    });
+}
+
+int mk_verify_deposits(mk_call* call, const uint8_t* data, const uint64_t* offs, const uint8_t* branches,
+                       const uint64_t* indices, uint64_t n, uint32_t depth, uint32_t tree_depth, const uint8_t* roots,
+                       uint32_t root_stride, uint8_t* ok) {
+    Scope S(call);
+    return S.done(host_verify_deposits(data, offs, branches, indices, n, depth, tree_depth, roots, root_stride, ok));
 }
 
 int mk_deposit_trie_leaves(mk_call* call, mk_trie* t, uint64_t first, uint64_t cnt, uint8_t* out) {

@@ -485,6 +485,50 @@ def deposit_trie_branch(levels: torch.Tensor, capacity: int, count: int, depth: 
     return out
 
 
+def deposit_trie_branches(levels: torch.Tensor, capacity: int, count: int, depth: int, as_of: int,
+                          indices: torch.Tensor, k: int = None, out: torch.Tensor = None,
+                          root_at: torch.Tensor = None) -> torch.Tensor:
+    """GenerateMerkleBranch for the k device ``indices`` (int64 / uint64, any
+    order) as of ``as_of`` <= count deposits, one launch: (k*depth*32,) uint8;
+    the root of that moment to ``root_at`` (32 B) when given
+    (mk_dev_deposit_trie_branches).  Nothing is read on the host, so a captured
+    call follows the indices tensor's contents at replay."""
+    dev = _dev(levels)
+    if k is None:
+        k = indices.numel()
+    if indices.element_size() != 8 or indices.numel() < k:
+        raise ValueError("indices: at least k 64-bit integers")
+    if out is None:
+        out = torch.empty(32 * depth * k, dtype=torch.uint8, device=levels.device)
+    elif out.numel() * out.element_size() < 32 * depth * k:
+        raise ValueError("branch buffer smaller than k x depth x 32 bytes")
+    _lib.invoke("mk_dev_deposit_trie_branches", _p(levels), capacity, count, depth, as_of, _p(indices), k, _p(out),
+                _p(root_at) if root_at is not None else None, _stream(levels.device), device=dev)
+    return out
+
+
+def verify_deposits(data: torch.Tensor, offs: torch.Tensor, branches: torch.Tensor, indices: torch.Tensor, n: int,
+                    depth: int, roots: torch.Tensor, root_stride: int = 0, tree_depth: int = 32,
+                    out: torch.Tensor = None) -> torch.Tensor:
+    """verifyDeposit for n deposits resident on the device (deposit i =
+    data[offs[i], offs[i+1]), ``offs`` n + 1 64-bit offsets): (n,) uint8, 1
+    where Hash(deposit) folds through its branch to the root -- ``roots``'
+    first 32 bytes for all of them (root_stride 0) or root i (root_stride 32)
+    (mk_dev_verify_deposits)."""
+    dev = _dev(branches)
+    if offs.element_size() != 8 or offs.numel() < n + 1 or indices.element_size() != 8 or indices.numel() < n:
+        raise ValueError("offs: n + 1 and indices: n 64-bit integers")
+    if branches.numel() * branches.element_size() < 32 * depth * n:
+        raise ValueError("branch buffer smaller than n x depth x 32 bytes")
+    if roots.numel() * roots.element_size() < (32 * n if root_stride else 32):
+        raise ValueError("root buffer too small")
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=branches.device)
+    _lib.invoke("mk_dev_verify_deposits", _p(data), _p(offs), _p(branches), _p(indices), n, depth, tree_depth,
+                _p(roots), root_stride, _p(out), _stream(branches.device), device=dev)
+    return out
+
+
 def list_tree_levels_bytes(capacity: int, item_len: int) -> int:
     """Bytes of the level array of a list tree with room for ``capacity`` items."""
     return _lib.load().mk_ssz_list_tree_levels_bytes(capacity, item_len)

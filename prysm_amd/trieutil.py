@@ -132,10 +132,14 @@ class DepositTrie:
 
     SaveLogs = save_logs
 
-    def generate_merkle_branch(self, index: int) -> List[bytes]:
+    def generate_merkle_branch(self, index: int, count: Optional[int] = None) -> List[bytes]:
         """GenerateMerkleBranch (deposit_trie.go:43-58): the sibling at each of
-        the `depth` levels; missing nodes read as 0^32."""
+        the `depth` levels; missing nodes read as 0^32.  ``count``: the branch
+        as of that many deposits (see generate_merkle_branches); None: now."""
         self._flush()
+        if count is not None:
+            raw = self.generate_merkle_branches([index], count).tobytes()
+            return [raw[32 * d:32 * d + 32] for d in range(self.depth)]
         if self._handle is None:
             return [ZERO] * self.depth
         out = ctypes.create_string_buffer(32 * self.depth)
@@ -144,6 +148,52 @@ class DepositTrie:
         return [raw[32 * d:32 * d + 32] for d in range(self.depth)]
 
     GenerateMerkleBranch = generate_merkle_branch
+
+    def _as_of(self, count: Optional[int]) -> int:
+        if count is None:
+            return self.deposit_count
+        if not 0 <= count <= self.deposit_count:
+            raise _lib.MerkleError(_lib.MK_EINVAL, f"count {count} outside 0..{self.deposit_count} deposits")
+        return count
+
+    def generate_merkle_branches(self, indices: Sequence[int], count: Optional[int] = None,
+                                 out: Optional[np.ndarray] = None) -> np.ndarray:
+        """GenerateMerkleBranch for every index in one device call, as of
+        ``count`` deposits (None: now): what the reference's trie answered
+        right after its count-th UpdateDepositTrie, so the branches verify
+        against the root of that moment (``root_at(count)``) -- the
+        state.LatestEth1Data.DepositRootHash32 that verifyDeposit checks
+        (core/blocks/block_operations.go:624-641) -- however many deposits
+        powchain has appended since.  Indices in any order, repeats allowed.
+        Returns (k, depth, 32) uint8 (``out``, when given: C-contiguous, that
+        shape); nothing is written when ``count`` is out of range."""
+        self._flush()
+        c = self._as_of(count)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = idx.size
+        if out is None:
+            out = np.empty((k, self.depth, 32), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.shape != (k, self.depth, 32) or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous (k, depth, 32) uint8 array")
+        if self._handle is None:
+            out[...] = 0
+            return out
+        _lib.invoke("mk_deposit_trie_branches", self._handle, c, _ptr(idx), k, _ptr(out), None, device=self._device)
+        return out
+
+    GenerateMerkleBranches = generate_merkle_branches
+
+    def root_at(self, count: Optional[int] = None) -> bytes:
+        """Root() as of ``count`` deposits (None: now); 0^32 for count 0."""
+        self._flush()
+        c = self._as_of(count)
+        if self._handle is None:
+            return ZERO
+        out = ctypes.create_string_buffer(32)
+        _lib.invoke("mk_deposit_trie_root_at", self._handle, c, out, device=self._device)
+        return out.raw
+
+    RootAt = root_at
 
     def root(self) -> bytes:
         """Root (deposit_trie.go:61-63): node 1, 0^32 when empty."""
@@ -189,3 +239,39 @@ def verify_merkle_branch(leaf: bytes, branch: Sequence[bytes], depth: int, index
 
 
 VerifyMerkleBranch = verify_merkle_branch
+
+
+def verify_deposits(deposit_datas: Sequence[bytes], branches, indices: Sequence[int], root_or_roots, depth: int,
+                    tree_depth: int = DEPOSIT_CONTRACT_TREE_DEPTH) -> List[bool]:
+    """verifyDeposit (core/blocks/block_operations.go:624-641) for a batch,
+    one GPU thread per deposit: Hash(deposit data), the fold of its branch,
+    the compare -- no leaf hashes cross the bus.  ``branches``: the
+    (k, depth, 32) array generate_merkle_branches returns, or a list of lists
+    of 32-byte siblings.  ``root_or_roots``: one 32-byte root for the whole
+    batch (a block's deposits against the state's deposit root) or one per
+    deposit."""
+    n = len(deposit_datas)
+    if n == 0:
+        return []
+    if isinstance(branches, np.ndarray):
+        br = np.ascontiguousarray(branches, dtype=np.uint8).reshape(-1)
+    else:
+        br = np.frombuffer(b"".join(bytes(b[i]) for b in branches for i in range(depth)), dtype=np.uint8)
+    if br.size != 32 * depth * n:
+        raise ValueError(f"branches hold {br.size} bytes, not {n} x {depth} x 32")
+    shared = isinstance(root_or_roots, (bytes, bytearray, memoryview))
+    roots = bytes(root_or_roots) if shared else b"".join(bytes(r) for r in root_or_roots)
+    if len(roots) != (32 if shared else 32 * n):
+        raise ValueError("one 32-byte root, or one per deposit")
+    rt = np.frombuffer(roots, dtype=np.uint8)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    if idx.size != n:
+        raise ValueError("one index per deposit")
+    data, offs = _flatten(deposit_datas)
+    ok = np.zeros(n, dtype=np.uint8)
+    _lib.invoke("mk_verify_deposits", _ptr(data), _ptr(offs), _ptr(br) if depth else None, _ptr(idx), n, depth,
+                tree_depth, _ptr(rt), 0 if shared else 32, _ptr(ok))
+    return [bool(x) for x in ok]
+
+
+VerifyDeposits = verify_deposits
