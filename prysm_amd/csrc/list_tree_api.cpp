@@ -1,30 +1,22 @@
 // The device-resident list tree: merkleHash (hash.go:194-239) of a list whose
-// levels stay in HBM -- build, update from the changed items only, the
-// mk_list_tree handle and the mk_*list_tree* entry points.
+// levels stay in HBM -- build, update from the changed items only and the
+// mk_*list_tree* entry points.  The mk_list_tree handle is
+// tree_handle.cpp's, with kListKind.
 #include "runtime.hpp"
 
 using namespace mk;
 using namespace mk::rt;
 
-// ---- list tree handle --------------------------------------------------------------------
-struct mk_list_tree {
-    std::mutex mu;
-    int dev = 0;
-    uint32_t item_len = 0;
-    uint64_t cap = 0, count = 0;  // items
-    DevBuf items, levels, root, idx, vals, ws;
-};
+struct mk_list_tree : TreeHandle {};
 
 namespace {
 
-// The handle rebuilds instead of climbing when count / kRebuildDiv <= dirty:
+// The handle rebuilds instead of climbing when count / MK_LIST_TREE_REBUILD_DIV <= dirty:
 // on the 2^24 x 32-B list an update of 2^15 random items (0.865 ms) is the
 // largest power of two still cheaper than a build (0.961 ms), 2^16 costs
 // 1.572 ms: a dirty fraction of 2^15 / 2^24 = 1/512 (tools/list_tree_probe.py,
 // profiles/list_tree/probe.json).
 #define MK_LIST_TREE_REBUILD_DIV 512
-constexpr uint64_t kRebuildDiv = MK_LIST_TREE_REBUILD_DIV;
-constexpr uint64_t kMaxWork = 1ull << 31;  // work items of one update launch
 
 uint64_t lt_per(uint32_t item_len) { return item_len < 128 ? 128 / item_len : 1; }
 uint64_t lt_chunks(uint64_t n, uint32_t item_len) { return ceil_div(n, lt_per(item_len)); }
@@ -50,42 +42,14 @@ int lt_check(uint64_t n, uint64_t capacity, uint32_t item_len) {
     return MK_OK;
 }
 
-// the climb's descriptor (k_list_tree_update, one slice of k_trees_update); d_arrive: zeroed arrival words
-mk::ListTreeArgs update_args(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
-                             uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32,
-                             void* d_arrive) {
-    mk::ListTreeArgs a{};
-    a.items = (const uint8_t*)d_items;
-    a.levels = (uint32_t*)d_levels;
-    a.idx = d_idx;
-    a.k_idx = k_idx;
-    a.n_old = n_old;
-    a.n_new = n_new;
-    a.cap_chunks = lt_chunks(capacity, item_len);
-    a.item_len = item_len;
-    a.per = (uint32_t)lt_per(item_len);
-    a.arrive = (uint64_t*)d_arrive;
-    a.root_out = (uint32_t*)d_root32;
-    return a;
-}
-
 int launch_update(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
                   uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32, void* d_ws, hipStream_t st) {
     const uint64_t T = k_idx + (n_new - n_old);
     const mk::ListTreeArgs a =
-        update_args(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_ws);
+        list_tree_args(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_ws);
     HIPCHK(hipMemsetAsync(d_ws, 0, 8 * std::max<uint64_t>(T, 1), st));
     hipLaunchKernelGGL(mk::k_list_tree_update, dim3(std::max<uint64_t>(ceil_div(2 * T, 256), 1)), dim3(256), 0, st, a);
     return launched();
-}
-
-int check_ptrs(const void* d_items, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
-               const void* d_root32, const void* d_ws) {
-    if (!d_root32 || !d_ws || (n && !d_items)) return fail(MK_EINVAL, "null pointer");
-    if (lt_chunks(capacity, item_len) > 1 && !d_levels) return fail(MK_EINVAL, "null level array");
-    if (((uintptr_t)d_levels % 16) || ((uintptr_t)d_root32 % 4) || ((uintptr_t)d_ws % 8))
-        return fail(MK_EINVAL, "level array (16 B), root (4 B) or workspace (8 B) misaligned");
-    return MK_OK;
 }
 
 // Every level and the root of n items.  One batched launch per level over
@@ -117,8 +81,49 @@ int dev_build(const void* d_items, uint64_t n, uint64_t capacity, uint32_t item_
     return launch_update(d_items, d_levels, nullptr, 0, n - 1, n, capacity, item_len, d_root32, d_ws, st);
 }
 
-int launch_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
-                   uint32_t item_len, const void* d_values, hipStream_t st) {
+int dev_update(void* d_items, uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_levels,
+               const uint64_t* d_idx, uint64_t k_idx, const void* d_values, void* d_root32, void* d_ws,
+               hipStream_t st) {
+    if (d_values) TRY(list_tree_scatter(d_items, d_idx, k_idx, n_old, n_new - n_old, item_len, d_values, st));
+    if (lt_chunks(n_new, item_len) <= 1) {
+        hipLaunchKernelGGL(mk::k_final_small, dim3(1), dim3(64), 0, st, (const uint8_t*)d_items, n_new * item_len,
+                           n_new, (uint8_t*)d_root32);
+        return launched();
+    }
+    return launch_update(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_ws, st);
+}
+
+// ---- what the handle (tree_handle.cpp) needs of this kind ----------------------------------
+const TreeKind kListKind = {
+    "list tree", "items", MK_LIST_TREE_REBUILD_DIV, false, lt_check,
+    [](const TreeHandle&, uint64_t) { return lt_update_ws(1); },
+    [](const TreeHandle&, uint64_t k) { return lt_update_ws(k); },
+    nullptr,
+    [](const TreeHandle& t, uint64_t n, hipStream_t st) {
+        return dev_build(t.items.p, n, t.cap, t.item_len, t.levels.p, t.root.p, t.ws.p, st);
+    },
+    [](const TreeHandle& t, uint64_t n_old, uint64_t n_new, const uint64_t* d_idx, uint64_t k_idx,
+       const void* d_values, hipStream_t st) {
+        return dev_update(t.items.p, n_old, n_new, t.cap, t.item_len, t.levels.p, d_idx, k_idx, d_values, t.root.p,
+                          t.ws.p, st);
+    },
+};
+
+}  // namespace
+
+namespace mk::rt {
+// what the registry tree (struct_tree_api.cpp) runs over its buffer of 32-B struct roots
+int list_tree_build32(const void* d_roots, uint64_t n, uint64_t capacity, void* d_levels, void* d_root32, void* d_ws,
+                      hipStream_t st) {
+    return dev_build(d_roots, n, capacity, 32, d_levels, d_root32, d_ws, st);
+}
+int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
+                       uint64_t n_new, uint64_t capacity, void* d_root32, void* d_ws, hipStream_t st) {
+    return launch_update(d_roots, d_levels, d_idx, k_idx, n_old, n_new, capacity, 32, d_root32, d_ws, st);
+}
+
+int list_tree_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
+                      uint32_t item_len, const void* d_values, hipStream_t st) {
     if (k_idx + n_app == 0) return MK_OK;
     const bool w8 = item_len % 8 == 0 && ((uintptr_t)d_items % 8) == 0 && ((uintptr_t)d_values % 8) == 0;
     const uint32_t unit = w8 ? 8 : 1;
@@ -128,21 +133,10 @@ int launch_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_
     return launched();
 }
 
-int dev_update(void* d_items, uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_levels,
-               const uint64_t* d_idx, uint64_t k_idx, const void* d_values, void* d_root32, void* d_ws,
-               hipStream_t st) {
-    if (d_values) TRY(launch_scatter(d_items, d_idx, k_idx, n_old, n_new - n_old, item_len, d_values, st));
-    if (lt_chunks(n_new, item_len) <= 1) {
-        hipLaunchKernelGGL(mk::k_final_small, dim3(1), dim3(64), 0, st, (const uint8_t*)d_items, n_new * item_len,
-                           n_new, (uint8_t*)d_root32);
-        return launched();
-    }
-    return launch_update(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_ws, st);
-}
-
+// The list tree's part of mk_dev_ssz_trees_update (its stage 0 is list_tree_scatter alone).
 // host-checkable arguments of mk_dev_ssz_list_tree_update (no device needed)
-int check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, uint64_t k_idx,
-                 uint64_t ws_bytes) {
+int list_tree_check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, uint64_t k_idx,
+                           uint64_t ws_bytes) {
     if (item_len == 0) return fail(MK_EINVAL, "item_len == 0");
     if (n_new < n_old)
         return fail(MK_EINVAL, "n_new %llu < n_old %llu (a list tree does not shrink)", (unsigned long long)n_new,
@@ -155,167 +149,32 @@ int check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t ite
     return MK_OK;
 }
 
-// ---- handle ------------------------------------------------------------------------------
-int tree_alloc(mk_list_tree* t, uint64_t cap) {
-    TRY(lt_check(0, cap, t->item_len));
-    TRY(grow(t->items, cap * t->item_len + 16));
-    TRY(grow(t->levels, 32 * lt_levels_nodes(lt_chunks(cap, t->item_len))));
-    t->cap = cap;
-    return MK_OK;
-}
-
-// all levels and the root of the items already in t->items
-int tree_rebuild(mk_list_tree* t, uint64_t n, hipStream_t st) {
-    TRY(grow(t->ws, lt_update_ws(1)));
-    return dev_build(t->items.p, n, t->cap, t->item_len, t->levels.p, t->root.p, t->ws.p, st);
-}
-
-bool rebuild_pays(uint64_t dirty, uint64_t count) { return dirty && count / kRebuildDiv <= dirty; }
-
-int tree_assign(mk_list_tree* t, const uint8_t* items, uint64_t n) {
-    if (!t || (n && !items)) return fail(MK_EINVAL, "null pointer");
-    std::lock_guard<std::mutex> tl(t->mu);
-    TRY(bind_dev(t->dev));
-    hipStream_t st = ctx()->stream;
-    if (n > t->cap) TRY(tree_alloc(t, n));
-    if (n) HIPCHK(hipMemcpyAsync(t->items.p, items, n * t->item_len, hipMemcpyHostToDevice, st));
-    TRY(tree_rebuild(t, n, st));
-    HIPCHK(hipStreamSynchronize(st));  // the caller's buffer is released after this
-    t->count = n;
-    return MK_OK;
-}
-
-int tree_update(mk_list_tree* t, const uint64_t* idx, const uint8_t* values, uint64_t k) {
-    if (!t || (k && (!idx || !values))) return fail(MK_EINVAL, "null pointer");
-    std::lock_guard<std::mutex> tl(t->mu);
-    for (uint64_t i = 0; i < k; ++i)
-        if (idx[i] >= t->count)
-            return fail(MK_EINVAL, "index %llu beyond %llu items", (unsigned long long)idx[i],
-                        (unsigned long long)t->count);
-    if (k == 0) return MK_OK;
-    // list[idx[j]] = values[j] in sequence: ascending indices, the last value of a repeated one
-    std::vector<uint64_t> order(k);
-    for (uint64_t i = 0; i < k; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return idx[a] < idx[b]; });
-    const uint32_t L = t->item_len;
-    std::vector<uint64_t> sidx;
-    std::vector<uint8_t> svals;
-    sidx.reserve(k);
-    svals.reserve(k * L);
-    for (uint64_t i = 0; i < k; ++i) {
-        if (i + 1 < k && idx[order[i + 1]] == idx[order[i]]) continue;
-        sidx.push_back(idx[order[i]]);
-        svals.insert(svals.end(), values + order[i] * L, values + (order[i] + 1) * L);
-    }
-    const uint64_t m = sidx.size();
-    if (m >= kMaxWork) return fail(MK_EINVAL, "%llu dirty items in one call", (unsigned long long)m);
-    TRY(bind_dev(t->dev));
-    hipStream_t st = ctx()->stream;
-    TRY(grow(t->idx, 8 * m));
-    TRY(grow(t->vals, m * L + 16));
-    TRY(grow(t->ws, lt_update_ws(m)));
-    HIPCHK(hipMemcpyAsync(t->idx.p, sidx.data(), 8 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(t->vals.p, svals.data(), m * L, hipMemcpyHostToDevice, st));
-    if (rebuild_pays(m, t->count)) {
-        TRY(launch_scatter(t->items.p, (const uint64_t*)t->idx.p, m, t->count, 0, L, t->vals.p, st));
-        TRY(tree_rebuild(t, t->count, st));
-    } else {
-        TRY(dev_update(t->items.p, t->count, t->count, t->cap, L, t->levels.p, (const uint64_t*)t->idx.p, m,
-                       t->vals.p, t->root.p, t->ws.p, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));  // sidx / svals are released after this
-    return MK_OK;
-}
-
-int tree_append(mk_list_tree* t, const uint8_t* items, uint64_t k) {
-    if (!t || (k && !items)) return fail(MK_EINVAL, "null pointer");
-    std::lock_guard<std::mutex> tl(t->mu);
-    if (k == 0) return MK_OK;
-    if (k >= kMaxWork || t->count + k < k) return fail(MK_EINVAL, "%llu items in one append", (unsigned long long)k);
-    TRY(bind_dev(t->dev));
-    hipStream_t st = ctx()->stream;
-    const uint32_t L = t->item_len;
-    const uint64_t n_new = t->count + k;
-    bool rebuild = rebuild_pays(k, n_new);
-    if (n_new > t->cap) {  // the layout depends on the capacity: double it, move the items, rebuild
-        const uint64_t ncap = std::max(2 * t->cap, n_new);
-        TRY(lt_check(n_new, ncap, L));
-        DevBuf ni;
-        TRY(grow(ni, ncap * L + 16));
-        if (t->count) HIPCHK(hipMemcpyAsync(ni.p, t->items.p, t->count * L, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(t->items.p);
-        t->items = ni;
-        TRY(grow(t->levels, 32 * lt_levels_nodes(lt_chunks(ncap, L))));
-        t->cap = ncap;
-        rebuild = true;
-    }
-    HIPCHK(hipMemcpyAsync((uint8_t*)t->items.p + t->count * L, items, k * L, hipMemcpyHostToDevice, st));
-    if (rebuild) {
-        TRY(tree_rebuild(t, n_new, st));
-    } else {
-        TRY(grow(t->ws, lt_update_ws(k)));
-        TRY(dev_update(t->items.p, t->count, n_new, t->cap, L, t->levels.p, nullptr, 0, nullptr, t->root.p, t->ws.p,
-                       st));
-    }
-    HIPCHK(hipStreamSynchronize(st));  // the caller's buffer is released after this
-    t->count = n_new;
-    return MK_OK;
-}
-
-int tree_root(mk_list_tree* t, uint8_t* root) {
-    if (!t || !root) return fail(MK_EINVAL, "null pointer");
-    std::lock_guard<std::mutex> tl(t->mu);
-    TRY(bind_dev(t->dev));
-    HIPCHK(hipMemcpyAsync(root, t->root.p, 32, hipMemcpyDeviceToHost, ctx()->stream));
-    HIPCHK(hipStreamSynchronize(ctx()->stream));
-    return MK_OK;
-}
-
-int tree_items(mk_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out) {
-    if (!t || (cnt && !out)) return fail(MK_EINVAL, "null pointer");
-    std::lock_guard<std::mutex> tl(t->mu);
-    if (first > t->count || cnt > t->count - first)
-        return fail(MK_EINVAL, "items [%llu, +%llu) beyond %llu items", (unsigned long long)first,
-                    (unsigned long long)cnt, (unsigned long long)t->count);
-    if (!cnt) return MK_OK;
-    TRY(bind_dev(t->dev));
-    hipStream_t st = ctx()->stream;
-    HIPCHK(hipMemcpyAsync(out, (const uint8_t*)t->items.p + first * t->item_len, cnt * t->item_len,
-                          hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return MK_OK;
-}
-
-}  // namespace
-
-// what the registry tree (struct_tree_api.cpp) runs over its buffer of 32-B struct roots
-namespace mk::rt {
-int list_tree_build32(const void* d_roots, uint64_t n, uint64_t capacity, void* d_levels, void* d_root32, void* d_ws,
-                      hipStream_t st) {
-    return dev_build(d_roots, n, capacity, 32, d_levels, d_root32, d_ws, st);
-}
-int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
-                       uint64_t n_new, uint64_t capacity, void* d_root32, void* d_ws, hipStream_t st) {
-    return launch_update(d_roots, d_levels, d_idx, k_idx, n_old, n_new, capacity, 32, d_root32, d_ws, st);
-}
-int list_tree_scatter(void* d_items, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old, uint64_t n_app,
-                      uint32_t item_len, const void* d_values, hipStream_t st) {
-    return launch_scatter(d_items, d_idx, k_idx, n_old, n_app, item_len, d_values, st);
-}
-// the list tree's part of mk_dev_ssz_trees_update (its stage 0 is list_tree_scatter alone)
-int list_tree_check_update(uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, uint64_t k_idx,
-                           uint64_t ws_bytes) {
-    return check_update(n_old, n_new, capacity, item_len, k_idx, ws_bytes);
-}
 int list_tree_check_ptrs(const void* d_items, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
                          const void* d_root32, const void* d_ws) {
-    return check_ptrs(d_items, n, capacity, item_len, d_levels, d_root32, d_ws);
+    if (!d_root32 || !d_ws || (n && !d_items)) return fail(MK_EINVAL, "null pointer");
+    if (lt_chunks(capacity, item_len) > 1 && !d_levels) return fail(MK_EINVAL, "null level array");
+    if (((uintptr_t)d_levels % 16) || ((uintptr_t)d_root32 % 4) || ((uintptr_t)d_ws % 8))
+        return fail(MK_EINVAL, "level array (16 B), root (4 B) or workspace (8 B) misaligned");
+    return MK_OK;
 }
+
+// the climb's descriptor (k_list_tree_update, one slice of k_trees_update); d_arrive: zeroed arrival words
 mk::ListTreeArgs list_tree_args(const void* d_items, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
                                 uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len, void* d_root32,
                                 void* d_arrive) {
-    return update_args(d_items, d_levels, d_idx, k_idx, n_old, n_new, capacity, item_len, d_root32, d_arrive);
+    mk::ListTreeArgs a{};
+    a.items = (const uint8_t*)d_items;
+    a.levels = (uint32_t*)d_levels;
+    a.idx = d_idx;
+    a.k_idx = k_idx;
+    a.n_old = n_old;
+    a.n_new = n_new;
+    a.cap_chunks = lt_chunks(capacity, item_len);
+    a.item_len = item_len;
+    a.per = (uint32_t)lt_per(item_len);
+    a.arrive = (uint64_t*)d_arrive;
+    a.root_out = (uint32_t*)d_root32;
+    return a;
 }
 }  // namespace mk::rt
 
@@ -342,7 +201,7 @@ int mk_dev_ssz_list_tree_build(mk_call* call, const void* d_items, uint64_t n, u
     int rc = lt_check(n, capacity, item_len);
     if (!rc && ws_bytes < lt_update_ws(1)) rc = fail(MK_ENOMEM, "workspace too small");
     if (!rc) rc = bind_stream((hipStream_t)stream);
-    if (!rc) rc = check_ptrs(d_items, n, capacity, item_len, d_levels, d_root32, d_ws);
+    if (!rc) rc = list_tree_check_ptrs(d_items, n, capacity, item_len, d_levels, d_root32, d_ws);
     if (!rc) rc = dev_build(d_items, n, capacity, item_len, d_levels, d_root32, d_ws, (hipStream_t)stream);
     return S.done(rc);
 }
@@ -351,9 +210,9 @@ int mk_dev_ssz_list_tree_update(mk_call* call, void* d_items, uint64_t n_old, ui
                                 uint32_t item_len, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
                                 const void* d_values, void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream) {
     Scope S(call);
-    int rc = check_update(n_old, n_new, capacity, item_len, k_idx, ws_bytes);
+    int rc = list_tree_check_update(n_old, n_new, capacity, item_len, k_idx, ws_bytes);
     if (!rc) rc = bind_stream((hipStream_t)stream);
-    if (!rc) rc = check_ptrs(d_items, n_new, capacity, item_len, d_levels, d_root32, d_ws);
+    if (!rc) rc = list_tree_check_ptrs(d_items, n_new, capacity, item_len, d_levels, d_root32, d_ws);
     if (!rc && k_idx && (!d_idx || ((uintptr_t)d_idx % 8))) rc = fail(MK_EINVAL, "null or misaligned index array");
     if (!rc)
         rc = dev_update(d_items, n_old, n_new, capacity, item_len, d_levels, d_idx, k_idx, d_values, d_root32, d_ws,
@@ -369,31 +228,12 @@ int mk_list_tree_new(mk_call* call, uint32_t item_len, uint64_t capacity, mk_lis
     if (!rc) rc = bind_call();
     if (rc) return S.done(rc);
     auto* t = new (std::nothrow) mk_list_tree();
-    if (!t) return S.done(fail(MK_ENOMEM, "list tree allocation failed"));
-    t->dev = t_bound;
-    t->item_len = item_len;
-    rc = tree_alloc(t, std::max<uint64_t>(capacity, 1));
-    if (!rc) rc = grow(t->root, 32);
-    if (!rc) rc = tree_rebuild(t, 0, ctx()->stream);  // merkleHash([])
-    if (!rc && hipStreamSynchronize(ctx()->stream) != hipSuccess) rc = fail(MK_EHIP, "hipStreamSynchronize failed");
-    if (rc) {
-        mk_list_tree_free(t);
-        return S.done(rc);
-    }
-    *out = t;
-    return S.done(MK_OK);
+    rc = tree_new(t, kListKind, item_len, capacity);
+    if (!rc) *out = t;
+    return S.done(rc);
 }
 
-void mk_list_tree_free(mk_list_tree* t) {
-    if (!t) return;
-    int saved = -1;
-    const bool restore = hipGetDevice(&saved) == hipSuccess;
-    (void)hipSetDevice(t->dev);
-    for (DevBuf* b : {&t->items, &t->levels, &t->root, &t->idx, &t->vals, &t->ws})
-        if (b->p) (void)hipFree(b->p);
-    if (restore) (void)hipSetDevice(saved);
-    delete t;
-}
+void mk_list_tree_free(mk_list_tree* t) { tree_free(t); }
 
 uint64_t mk_list_tree_count(const mk_list_tree* t) { return t ? t->count : 0; }
 
@@ -419,7 +259,7 @@ int mk_list_tree_root(mk_call* call, mk_list_tree* t, uint8_t root[32]) {
 
 int mk_list_tree_items(mk_call* call, mk_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out) {
     Scope S(call);
-    return S.done(tree_items(t, first, cnt, out));
+    return S.done(tree_read(t, first, cnt, out));
 }
 
 }  // extern "C"

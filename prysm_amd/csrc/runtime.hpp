@@ -167,6 +167,7 @@ int struct_launch_roots(const void* d_rec, uint64_t n, const mk::HostSpec& sp, v
                         hipStream_t st);
 
 // ---- list tree over 32-B items (list_tree_api.cpp) -----------------------------------
+constexpr uint64_t kMaxWork = 1ull << 31;  // work items of one tree update launch
 int list_tree_build32(const void* d_roots, uint64_t n, uint64_t capacity, void* d_levels, void* d_root32, void* d_ws,
                       hipStream_t st);  // d_ws: 256 B
 int list_tree_update32(const void* d_roots, void* d_levels, const uint64_t* d_idx, uint64_t k_idx, uint64_t n_old,
@@ -206,6 +207,43 @@ int bytes_tree_check_ptrs(const void* d_elems, uint64_t n, uint64_t capacity, co
                           const void* d_levels, const void* d_root32, const void* d_ws);
 int bytes_tree_stage0(void* d_elems, uint64_t n_old, uint64_t n_new, uint32_t elem_len, void* d_digests,
                       const uint64_t* d_idx, uint64_t k_idx, const void* d_values, hipStream_t st);
+
+// ---- the host handle of a resident tree (tree_handle.cpp) -------------------------------
+// One implementation under mk_list_tree, mk_struct_list_tree and
+// mk_bytes_list_tree; what differs between the kinds is a TreeKind, defined
+// next to the kind's dev_build / dev_update.
+struct TreeHandle;
+struct TreeKind {
+    const char* name;      // "list tree"
+    const char* noun;      // "items"
+    uint64_t rebuild_div;  // rebuild instead of climbing when count / rebuild_div <= dirty
+    bool level0;           // a 32-B entry per item (struct root, element digest) under the levels
+    int (*check_shape)(uint64_t n, uint64_t capacity, uint32_t item_len);
+    uint64_t (*build_ws)(const TreeHandle& t, uint64_t n);   // workspace of dev_build of n items
+    uint64_t (*update_ws)(const TreeHandle& t, uint64_t k);  // ... of dev_update of k work items
+    int (*check_values)(const TreeHandle& t, const uint8_t* values, uint64_t n);  // host check; null: none
+    // every level and the root of the n items in t.items; the climb from the changed items
+    int (*dev_build)(const TreeHandle& t, uint64_t n, hipStream_t st);
+    int (*dev_update)(const TreeHandle& t, uint64_t n_old, uint64_t n_new, const uint64_t* d_idx, uint64_t k_idx,
+                      const void* d_values, hipStream_t st);
+};
+struct TreeHandle {
+    const TreeKind* kind = nullptr;
+    std::mutex mu;
+    int dev = 0;
+    uint32_t item_len = 0;
+    uint64_t cap = 0, count = 0;  // items
+    DevBuf items, level0, levels, root, idx, vals, ws;
+    virtual ~TreeHandle() = default;  // a kind may add state of its own (the struct kind's layout)
+};
+// mk_*_new after the kind's argument checks and bind_call(): takes t (null: its allocation failed), frees it on failure
+int tree_new(TreeHandle* t, const TreeKind& kind, uint32_t item_len, uint64_t capacity);
+void tree_free(TreeHandle* t);
+int tree_assign(TreeHandle* t, const uint8_t* values, uint64_t n);
+int tree_update(TreeHandle* t, const uint64_t* idx, const uint8_t* values, uint64_t k);
+int tree_append(TreeHandle* t, const uint8_t* values, uint64_t k);
+int tree_root(TreeHandle* t, uint8_t* root);
+int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out);
 
 // ---- multi-device (multi_api.cpp) ------------------------------------------------
 int host_merkle_multi(const uint8_t* items, uint64_t n, uint32_t item_len, int nshards, const int* devs_in,

@@ -1,0 +1,185 @@
+// The host handle of a device-resident tree, once for the three kinds
+// (mk_list_tree §5d, mk_struct_list_tree §5e, mk_bytes_list_tree §5f): the
+// list, its level 0 and its levels in HBM, assign / update / append / root /
+// read-back under one mutex.  What a kind does differently is its TreeKind
+// (runtime.hpp), defined in list_tree_api, struct_tree_api, bytes_tree_api.
+#include "runtime.hpp"
+
+using namespace mk;
+
+namespace mk::rt {
+namespace {
+
+// level 0 and the levels for `cap` items (the item buffer is the caller's: an append has to move it)
+int grow_levels(TreeHandle* t, uint64_t cap) {
+    if (t->kind->level0) TRY(grow(t->level0, 32 * cap + 16));  // every entry is computed again by the rebuild
+    return grow(t->levels, mk_ssz_list_tree_levels_bytes(cap, t->kind->level0 ? 32 : t->item_len));
+}
+
+int alloc(TreeHandle* t, uint64_t cap) {
+    TRY(t->kind->check_shape(0, cap, t->item_len));
+    TRY(grow(t->items, cap * t->item_len + 16));
+    TRY(grow_levels(t, cap));
+    t->cap = cap;
+    return MK_OK;
+}
+
+// level 0, all levels and the root of the items already in t->items
+int rebuild(TreeHandle* t, uint64_t n, hipStream_t st) {
+    TRY(grow(t->ws, t->kind->build_ws(*t, n)));
+    return t->kind->dev_build(*t, n, st);
+}
+
+bool rebuild_pays(const TreeHandle* t, uint64_t dirty, uint64_t count) {
+    return dirty && count / t->kind->rebuild_div <= dirty;
+}
+
+int check_values(const TreeHandle* t, const uint8_t* values, uint64_t n) {
+    return t->kind->check_values ? t->kind->check_values(*t, values, n) : MK_OK;
+}
+
+}  // namespace
+
+int tree_new(TreeHandle* t, const TreeKind& kind, uint32_t item_len, uint64_t capacity) {
+    if (!t) return fail(MK_ENOMEM, "%s allocation failed", kind.name);
+    t->kind = &kind;
+    t->dev = t_bound;
+    t->item_len = item_len;
+    int rc = alloc(t, std::max<uint64_t>(capacity, 1));
+    if (!rc) rc = grow(t->root, 32);
+    if (!rc) rc = rebuild(t, 0, ctx()->stream);  // merkleHash([])
+    if (!rc && hipStreamSynchronize(ctx()->stream) != hipSuccess) rc = fail(MK_EHIP, "hipStreamSynchronize failed");
+    if (rc) tree_free(t);
+    return rc;
+}
+
+void tree_free(TreeHandle* t) {
+    if (!t) return;
+    int saved = -1;
+    const bool restore = hipGetDevice(&saved) == hipSuccess;
+    (void)hipSetDevice(t->dev);
+    for (DevBuf* b : {&t->items, &t->level0, &t->levels, &t->root, &t->idx, &t->vals, &t->ws})
+        if (b->p) (void)hipFree(b->p);
+    if (restore) (void)hipSetDevice(saved);
+    delete t;
+}
+
+int tree_assign(TreeHandle* t, const uint8_t* values, uint64_t n) {
+    if (!t || (n && !values)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    TRY(check_values(t, values, n));
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    if (n > t->cap) TRY(alloc(t, n));
+    if (n) HIPCHK(hipMemcpyAsync(t->items.p, values, n * t->item_len, hipMemcpyHostToDevice, st));
+    TRY(rebuild(t, n, st));
+    HIPCHK(hipStreamSynchronize(st));  // the caller's buffer is released after this
+    t->count = n;
+    return MK_OK;
+}
+
+int tree_update(TreeHandle* t, const uint64_t* idx, const uint8_t* values, uint64_t k) {
+    if (!t || (k && (!idx || !values))) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    const char* noun = t->kind->noun;
+    for (uint64_t i = 0; i < k; ++i)
+        if (idx[i] >= t->count)
+            return fail(MK_EINVAL, "index %llu beyond %llu %s", (unsigned long long)idx[i],
+                        (unsigned long long)t->count, noun);
+    if (k == 0) return MK_OK;
+    TRY(check_values(t, values, k));
+    // list[idx[j]] = values[j] in sequence: ascending indices, the last value of a repeated one
+    std::vector<uint64_t> order(k);
+    for (uint64_t i = 0; i < k; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return idx[a] < idx[b]; });
+    const uint32_t L = t->item_len;
+    std::vector<uint64_t> sidx;
+    std::vector<uint8_t> svals;
+    sidx.reserve(k);
+    svals.reserve(k * L);
+    for (uint64_t i = 0; i < k; ++i) {
+        if (i + 1 < k && idx[order[i + 1]] == idx[order[i]]) continue;
+        sidx.push_back(idx[order[i]]);
+        svals.insert(svals.end(), values + order[i] * L, values + (order[i] + 1) * L);
+    }
+    const uint64_t m = sidx.size();
+    if (m >= kMaxWork) return fail(MK_EINVAL, "%llu dirty %s in one call", (unsigned long long)m, noun);
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    TRY(grow(t->idx, 8 * m));
+    TRY(grow(t->vals, m * L + 16));
+    HIPCHK(hipMemcpyAsync(t->idx.p, sidx.data(), 8 * m, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t->vals.p, svals.data(), m * L, hipMemcpyHostToDevice, st));
+    if (rebuild_pays(t, m, t->count)) {
+        TRY(list_tree_scatter(t->items.p, (const uint64_t*)t->idx.p, m, t->count, 0, L, t->vals.p, st));
+        TRY(rebuild(t, t->count, st));
+    } else {
+        TRY(grow(t->ws, t->kind->update_ws(*t, m)));
+        TRY(t->kind->dev_update(*t, t->count, t->count, (const uint64_t*)t->idx.p, m, t->vals.p, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // sidx / svals are released after this
+    return MK_OK;
+}
+
+int tree_append(TreeHandle* t, const uint8_t* values, uint64_t k) {
+    if (!t || (k && !values)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    if (k == 0) return MK_OK;
+    if (k >= kMaxWork || t->count + k < k)
+        return fail(MK_EINVAL, "%llu %s in one append", (unsigned long long)k, t->kind->noun);
+    TRY(check_values(t, values, k));
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    const uint32_t L = t->item_len;
+    const uint64_t n_new = t->count + k;
+    bool rebuild_all = rebuild_pays(t, k, n_new);
+    if (n_new > t->cap) {  // the layout depends on the capacity: double it, move the items, rebuild
+        const uint64_t ncap = std::max(2 * t->cap, n_new);
+        TRY(t->kind->check_shape(n_new, ncap, L));
+        DevBuf ni;
+        TRY(grow(ni, ncap * L + 16));
+        if (t->count) HIPCHK(hipMemcpyAsync(ni.p, t->items.p, t->count * L, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(t->items.p);
+        t->items = ni;
+        TRY(grow_levels(t, ncap));
+        t->cap = ncap;
+        rebuild_all = true;
+    }
+    HIPCHK(hipMemcpyAsync((uint8_t*)t->items.p + t->count * L, values, k * L, hipMemcpyHostToDevice, st));
+    if (rebuild_all) {
+        TRY(rebuild(t, n_new, st));
+    } else {
+        TRY(grow(t->ws, t->kind->update_ws(*t, k)));
+        TRY(t->kind->dev_update(*t, t->count, n_new, nullptr, 0, nullptr, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // the caller's buffer is released after this
+    t->count = n_new;
+    return MK_OK;
+}
+
+int tree_root(TreeHandle* t, uint8_t* root) {
+    if (!t || !root) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    TRY(bind_dev(t->dev));
+    HIPCHK(hipMemcpyAsync(root, t->root.p, 32, hipMemcpyDeviceToHost, ctx()->stream));
+    HIPCHK(hipStreamSynchronize(ctx()->stream));
+    return MK_OK;
+}
+
+int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out) {
+    if (!t || (cnt && !out)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    if (first > t->count || cnt > t->count - first)
+        return fail(MK_EINVAL, "%s [%llu, +%llu) beyond %llu %s", t->kind->noun, (unsigned long long)first,
+                    (unsigned long long)cnt, (unsigned long long)t->count, t->kind->noun);
+    if (!cnt) return MK_OK;
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    const uint32_t L = t->item_len;
+    HIPCHK(hipMemcpyAsync(out, (const uint8_t*)t->items.p + first * L, cnt * L, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MK_OK;
+}
+
+}  // namespace mk::rt

@@ -45,38 +45,51 @@ from . import _lib
 from .hashutil import _ptr
 
 
-class ListTree:
-    """A list of fixed-length items and its merkleHash tree, device-resident."""
+class _Tree:
+    """What the three handles share: a list of ``_len``-byte values behind the
+    ``mk_<_prefix>_*`` entry points (one handle core in C: csrc/tree_handle.cpp)."""
 
-    def __init__(self, item_len: int, capacity: int = 0, device: int = -1):
-        self.item_len = int(item_len)
+    _prefix = ""    # C symbol prefix: mk_<_prefix>_new, _assign, ...
+    _noun = ""      # what a value is called in messages
+    _one = ""       # ValueError text of update(): "one ... per index"
+    _reader = ""    # name of the read-back entry point and method
+
+    def __init__(self, value_len: int, *new_args, device: int = -1):
+        self._len = int(value_len)
         self._device = device
         self._handle = None
         h = ctypes.c_void_p()
-        _lib.invoke("mk_list_tree_new", self.item_len, int(capacity), ctypes.byref(h), device=device)
+        _lib.invoke(f"mk_{self._prefix}_new", self._len, *new_args, ctypes.byref(h), device=device)
         self._handle = h
 
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and _lib is not None:
             try:
-                _lib.load().mk_list_tree_free(h)
+                getattr(_lib.load(), f"mk_{self._prefix}_free")(h)
             except Exception:
                 pass
 
     def __len__(self) -> int:
-        return int(_lib.load().mk_list_tree_count(self._handle))
+        return int(getattr(_lib.load(), f"mk_{self._prefix}_count")(self._handle))
+
+    def _bytes(self, values) -> np.ndarray:
+        return np.ascontiguousarray(values, dtype=np.uint8)
 
     def _flat(self, values) -> np.ndarray:
-        a = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1)
-        if a.size % self.item_len:
-            raise ValueError(f"{a.size} bytes are not a whole number of {self.item_len}-byte items")
+        a = self._bytes(values).reshape(-1)
+        if a.size % self._len:
+            raise ValueError(f"{a.size} bytes are not a whole number of {self._len}-byte {self._noun}")
         return a
 
-    def assign(self, items) -> None:
-        """Replace the whole list (uint8 array of n * item_len bytes, any shape)."""
-        a = self._flat(items)
-        _lib.invoke("mk_list_tree_assign", self._handle, _ptr(a), a.size // self.item_len, device=self._device)
+    def _call(self, op: str, *args):
+        _lib.invoke(f"mk_{self._prefix}_{op}", self._handle, *args, device=self._device)
+
+    def assign(self, values) -> None:
+        """Replace the whole list (uint8 array of n * value_len bytes, any
+        shape; a StructListTree also takes a structured array)."""
+        a = self._flat(values)
+        self._call("assign", _ptr(a), a.size // self._len)
 
     def update(self, indices, values) -> None:
         """``list[indices[j]] = values[j]`` for every j in order (any order,
@@ -84,163 +97,68 @@ class ListTree:
         and changes nothing."""
         idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
         a = self._flat(values)
-        if a.size != idx.size * self.item_len:
-            raise ValueError("one item_len-byte value per index")
-        _lib.invoke("mk_list_tree_update", self._handle, _ptr(idx), _ptr(a), idx.size, device=self._device)
+        if a.size != idx.size * self._len:
+            raise ValueError(self._one)
+        self._call("update", _ptr(idx), _ptr(a), idx.size)
 
-    def append(self, items) -> None:
-        """Append items; past the capacity the tree doubles it and rebuilds."""
-        a = self._flat(items)
-        _lib.invoke("mk_list_tree_append", self._handle, _ptr(a), a.size // self.item_len, device=self._device)
+    def append(self, values) -> None:
+        """Append values; past the capacity the tree doubles it and rebuilds."""
+        a = self._flat(values)
+        self._call("append", _ptr(a), a.size // self._len)
 
     def root(self) -> bytes:
-        """merkleHash of the current items."""
+        """merkleHash (ListTree) / TreeHash (the other two) of the current list."""
         out = ctypes.create_string_buffer(32)
-        _lib.invoke("mk_list_tree_root", self._handle, out, device=self._device)
+        self._call("root", out)
         return out.raw
 
-    def items(self, first: int = 0, count: int = None) -> np.ndarray:
-        """Items [first, first + count) read back as a (count, item_len) uint8 array."""
+    def _read(self, first: int = 0, count: int = None) -> np.ndarray:
+        """Values [first, first + count) read back as a (count, value_len) uint8 array."""
         if count is None:
             count = len(self) - first
-        out = np.empty((max(count, 0), self.item_len), dtype=np.uint8)
-        _lib.invoke("mk_list_tree_items", self._handle, first, count, _ptr(out), device=self._device)
+        out = np.empty((max(count, 0), self._len), dtype=np.uint8)
+        self._call(self._reader, first, count, _ptr(out))
         return out
 
 
-class StructListTree:
+class ListTree(_Tree):
+    """A list of fixed-length items and its merkleHash tree, device-resident."""
+
+    _prefix, _noun, _one, _reader = "list_tree", "items", "one item_len-byte value per index", "items"
+    items = _Tree._read
+
+    def __init__(self, item_len: int, capacity: int = 0, device: int = -1):
+        super().__init__(item_len, int(capacity), device=device)
+        self.item_len = self._len
+
+
+class StructListTree(_Tree):
     """A list of flat fixed-layout records (``fields`` = [(kind, offset, len)]
     as in ``registry.VALIDATOR_FIELDS``) and the tree of its TreeHash,
     device-resident: records, struct roots and levels."""
 
+    _prefix, _noun, _one, _reader = "struct_list_tree", "records", "one record per index", "records"
+    records = _Tree._read
+
     def __init__(self, record_len: int, fields, capacity: int = 0, device: int = -1):
         from .registry import _fields
 
-        self.record_len = int(record_len)
         self.fields = list(fields)
-        self._device = device
-        self._handle = None
-        h = ctypes.c_void_p()
-        _lib.invoke("mk_struct_list_tree_new", self.record_len, _fields(self.fields), len(self.fields),
-                    int(capacity), ctypes.byref(h), device=device)
-        self._handle = h
+        super().__init__(record_len, _fields(self.fields), len(self.fields), int(capacity), device=device)
+        self.record_len = self._len
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and _lib is not None:
-            try:
-                _lib.load().mk_struct_list_tree_free(h)
-            except Exception:
-                pass
-
-    def __len__(self) -> int:
-        return int(_lib.load().mk_struct_list_tree_count(self._handle))
-
-    def _flat(self, records) -> np.ndarray:
-        a = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
-        if a.size % self.record_len:
-            raise ValueError(f"{a.size} bytes are not a whole number of {self.record_len}-byte records")
-        return a
-
-    def assign(self, records) -> None:
-        """Replace the whole list (n records: a structured or uint8 array)."""
-        a = self._flat(records)
-        _lib.invoke("mk_struct_list_tree_assign", self._handle, _ptr(a), a.size // self.record_len,
-                    device=self._device)
-
-    def update(self, indices, records) -> None:
-        """``list[indices[j]] = records[j]`` for every j in order (any order,
-        repeats allowed: the last value wins).  An index >= len(self) raises
-        and changes nothing."""
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-        a = self._flat(records)
-        if a.size != idx.size * self.record_len:
-            raise ValueError("one record per index")
-        _lib.invoke("mk_struct_list_tree_update", self._handle, _ptr(idx), _ptr(a), idx.size, device=self._device)
-
-    def append(self, records) -> None:
-        """Append records; past the capacity the tree doubles it and rebuilds."""
-        a = self._flat(records)
-        _lib.invoke("mk_struct_list_tree_append", self._handle, _ptr(a), a.size // self.record_len,
-                    device=self._device)
-
-    def root(self) -> bytes:
-        """TreeHash of the current list of records."""
-        out = ctypes.create_string_buffer(32)
-        _lib.invoke("mk_struct_list_tree_root", self._handle, out, device=self._device)
-        return out.raw
-
-    def records(self, first: int = 0, count: int = None) -> np.ndarray:
-        """Records [first, first + count) read back as a (count, record_len) uint8 array."""
-        if count is None:
-            count = len(self) - first
-        out = np.empty((max(count, 0), self.record_len), dtype=np.uint8)
-        _lib.invoke("mk_struct_list_tree_records", self._handle, first, count, _ptr(out), device=self._device)
-        return out
+    def _bytes(self, records) -> np.ndarray:  # a structured array as its bytes: no dtype conversion
+        return np.ascontiguousarray(records).view(np.uint8)
 
 
-class BytesListTree:
+class BytesListTree(_Tree):
     """A list of byte strings of ``elem_len`` bytes each (``[][N]byte``) and
     the tree of its TreeHash, device-resident: elements, element digests and
     levels."""
 
+    _prefix, _noun, _one, _reader = "bytes_list_tree", "elements", "one elem_len-byte element per index", "elems"
+    elems = _Tree._read
+
     def __init__(self, elem_len: int, capacity: int = 0, device: int = -1):
-        self.elem_len = int(elem_len)
-        self._device = device
-        self._handle = None
-        h = ctypes.c_void_p()
-        _lib.invoke("mk_bytes_list_tree_new", self.elem_len, int(capacity), ctypes.byref(h), device=device)
-        self._handle = h
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and _lib is not None:
-            try:
-                _lib.load().mk_bytes_list_tree_free(h)
-            except Exception:
-                pass
-
-    def __len__(self) -> int:
-        return int(_lib.load().mk_bytes_list_tree_count(self._handle))
-
-    def _flat(self, elems) -> np.ndarray:
-        a = np.ascontiguousarray(elems, dtype=np.uint8).reshape(-1)
-        if a.size % self.elem_len:
-            raise ValueError(f"{a.size} bytes are not a whole number of {self.elem_len}-byte elements")
-        return a
-
-    def assign(self, elems) -> None:
-        """Replace the whole list (uint8 array of n * elem_len bytes, any shape)."""
-        a = self._flat(elems)
-        _lib.invoke("mk_bytes_list_tree_assign", self._handle, _ptr(a), a.size // self.elem_len,
-                    device=self._device)
-
-    def update(self, indices, elems) -> None:
-        """``list[indices[j]] = elems[j]`` for every j in order (any order,
-        repeats allowed: the last value wins).  An index >= len(self) raises
-        and changes nothing."""
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-        a = self._flat(elems)
-        if a.size != idx.size * self.elem_len:
-            raise ValueError("one elem_len-byte element per index")
-        _lib.invoke("mk_bytes_list_tree_update", self._handle, _ptr(idx), _ptr(a), idx.size, device=self._device)
-
-    def append(self, elems) -> None:
-        """Append elements; past the capacity the tree doubles it and rebuilds."""
-        a = self._flat(elems)
-        _lib.invoke("mk_bytes_list_tree_append", self._handle, _ptr(a), a.size // self.elem_len,
-                    device=self._device)
-
-    def root(self) -> bytes:
-        """TreeHash of the current list of byte strings."""
-        out = ctypes.create_string_buffer(32)
-        _lib.invoke("mk_bytes_list_tree_root", self._handle, out, device=self._device)
-        return out.raw
-
-    def elems(self, first: int = 0, count: int = None) -> np.ndarray:
-        """Elements [first, first + count) read back as a (count, elem_len) uint8 array."""
-        if count is None:
-            count = len(self) - first
-        out = np.empty((max(count, 0), self.elem_len), dtype=np.uint8)
-        _lib.invoke("mk_bytes_list_tree_elems", self._handle, first, count, _ptr(out), device=self._device)
-        return out
+        super().__init__(elem_len, int(capacity), device=device)
+        self.elem_len = self._len
