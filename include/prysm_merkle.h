@@ -623,6 +623,70 @@ int mk_dev_ssz_trees_update(mk_call* call, const mk_tree_update* trees, uint32_t
                             uint32_t container_len, void* d_container_root32, void* d_ws, uint64_t ws_bytes,
                             void* stream);
 
+/* ---- a set of device-resident trees behind one host handle ---------------- */
+/* mk_tree_set is the handle form of mk_dev_ssz_trees_update for host callers
+ * (cgo has no device pointers): it owns up to MK_TREES_MAX resident trees of
+ * the three kinds and, in HBM, the hash message (container_len = 0 ..
+ * MK_CONTAINER_MAX bytes; 0: no container) of the struct whose list fields
+ * they are.  Changes are collected on the host; a root is ONE upload of every
+ * tree's changes and the message, mk_dev_ssz_trees_update over all the trees,
+ * one 32-B read-back and one synchronise.  Every rule below is what
+ * mk_list_tree / mk_struct_list_tree / mk_bytes_list_tree promise of one tree.
+ * new: needs no device; the set lives on call->device (-1: the device current
+ *   when the first tree is added) and every call runs there and restores the
+ *   caller's device, free included.
+ * add: at any time.  kind = MK_TREE_LIST / STRUCT / BYTES, item_len = item /
+ *   record / element length, fields / nfields the record layout (STRUCT only,
+ *   copied), container_off the offset of the tree's root in the message or
+ *   MK_NO_CONTAINER.  The new tree is empty, its root merkleHash([]); *tree =
+ *   0, 1, ... is its number.  MK_EINVAL, before any device is needed: a 17th
+ *   tree, an unknown kind, fields missing (STRUCT) or given (LIST, BYTES), the
+ *   kind's own shape errors (item_len == 0, a bad layout, capacity * item_len
+ *   overflowing), a container_off that is not 4-B aligned, leaves the message
+ *   or overlaps another tree's 32 bytes.
+ * put: the other fields' outputs into the message; a range that leaves the
+ *   message or touches a tree's 32-B root range is MK_EINVAL and nothing is
+ *   written.  No device call.
+ * update: list[idx[j]] = values[j] in sequence (any order; of a repeated index
+ *   the last value wins); an index >= count (pending appends included) is
+ *   MK_EINVAL and nothing changes; an index inside the pending appends changes
+ *   that pending value.  append: values behind the list.  A STRUCT tree's
+ *   records pass the VARBYTES length check here, not at the flush.  Both only
+ *   record the change: no device call, no synchronise; the caller's buffers
+ *   are copied and free on return.
+ * assign: replaces the list (a shorter one too), drops the tree's pending
+ *   changes, and goes through the build entry at once.
+ * root / tree_root / items flush first: every tree's ascending, de-duplicated
+ *   indices and values, then its appended values, in one pinned staging buffer
+ *   (indices at 8-B, values at 16-B boundaries) sent by one copy; a tree that
+ *   outgrew its capacity doubles it, moves its items and rebuilds; a tree whose
+ *   dirty share reaches its kind's (count / 512, / 32, / 256 <= dirty: DESIGN.md
+ *   §5d-§5f) takes the write-through and the build; both enter the update with
+ *   nothing dirty, so their roots still reach the message.  With nothing
+ *   changed the same root comes back.  A failed flush leaves the pending
+ *   changes in place: the next call tries again, or the caller frees the set.
+ * root: the hash of the message (K(message), every tree's root at its offset);
+ *   MK_EINVAL when container_len == 0 or no tree takes part in the container.
+ *   tree_root: one tree's root, always.  items: [first, first + cnt) of one
+ *   tree, cnt x item_len bytes.  count: its length, pending appends included.
+ * One mutex per set: any thread may call, two sets are independent.
+ * Replaces: ssz.TreeHash (shared/ssz/hash.go:23-239) of a long-lived struct of
+ * lists -- a pb.BeaconState -- between two slots. */
+typedef struct mk_tree_set mk_tree_set;
+int mk_tree_set_new(mk_call* call, uint32_t container_len, mk_tree_set** out);
+void mk_tree_set_free(mk_tree_set* s);
+int mk_tree_set_add(mk_call* call, mk_tree_set* s, uint32_t kind, uint32_t item_len, const mk_field* fields,
+                    uint32_t nfields, uint64_t capacity, uint32_t container_off, uint32_t* tree);
+int mk_tree_set_put(mk_call* call, mk_tree_set* s, uint32_t off, const uint8_t* bytes, uint32_t len);
+int mk_tree_set_assign(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t n);
+int mk_tree_set_update(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, const uint8_t* values,
+                       uint64_t k);
+int mk_tree_set_append(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t k);
+uint64_t mk_tree_set_count(const mk_tree_set* s, uint32_t tree);
+int mk_tree_set_root(mk_call* call, mk_tree_set* s, uint8_t root[32]);
+int mk_tree_set_tree_root(mk_call* call, mk_tree_set* s, uint32_t tree, uint8_t root[32]);
+int mk_tree_set_items(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t first, uint64_t cnt, uint8_t* out);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

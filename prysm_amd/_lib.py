@@ -159,6 +159,17 @@ _SIGS = {
     "mk_bytes_list_tree_elems": (_int, [_cp, _vp, _u64, _u64, _vp]),
     "mk_ssz_trees_update_workspace_bytes": (_u64, [_vp, _u32]),
     "mk_dev_ssz_trees_update": (_int, [_cp, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "mk_tree_set_new": (_int, [_cp, _u32, _vp]),
+    "mk_tree_set_free": (None, [_vp]),
+    "mk_tree_set_add": (_int, [_cp, _vp, _u32, _u32, _vp, _u32, _u64, _u32, _vp]),
+    "mk_tree_set_put": (_int, [_cp, _vp, _u32, _vp, _u32]),
+    "mk_tree_set_assign": (_int, [_cp, _vp, _u32, _vp, _u64]),
+    "mk_tree_set_update": (_int, [_cp, _vp, _u32, _vp, _vp, _u64]),
+    "mk_tree_set_append": (_int, [_cp, _vp, _u32, _vp, _u64]),
+    "mk_tree_set_count": (_u64, [_vp, _u32]),
+    "mk_tree_set_root": (_int, [_cp, _vp, _vp]),
+    "mk_tree_set_tree_root": (_int, [_cp, _vp, _u32, _vp]),
+    "mk_tree_set_items": (_int, [_cp, _vp, _u32, _u64, _u64, _vp]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),

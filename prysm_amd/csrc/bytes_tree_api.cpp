@@ -119,6 +119,9 @@ int bytes_tree_stage0(void* d_elems, uint64_t n_old, uint64_t n_new, uint32_t el
                        elem_len, fast32, d_idx, k_idx, n_old, n_app, (uint4*)d_digests);
     return launched();
 }
+
+TreeHandle* bytes_tree_handle() { return new (std::nothrow) mk_bytes_list_tree(); }
+const TreeKind& bytes_tree_kind() { return kBytesKind; }
 }  // namespace mk::rt
 
 extern "C" {

@@ -176,6 +176,9 @@ mk::ListTreeArgs list_tree_args(const void* d_items, void* d_levels, const uint6
     a.root_out = (uint32_t*)d_root32;
     return a;
 }
+
+TreeHandle* list_tree_handle() { return new (std::nothrow) mk_list_tree(); }
+const TreeKind& list_tree_kind() { return kListKind; }
 }  // namespace mk::rt
 
 extern "C" {

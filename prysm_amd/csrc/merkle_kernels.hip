@@ -4715,4 +4715,50 @@ __global__ __launch_bounds__(256) void k_bytes_tree_digest(const uint8_t* __rest
     digests[2 * x + 1] = make_uint4(d[4], d[5], d[6], d[7]);
 }
 
+// ----------------------------------------------------------------------------
+// Stage 0 of several resident trees in one launch: slice
+// blockIdx.y of the grid is one segment of g.s -- k_list_tree_scatter's rule
+// (values into an item buffer, struct roots into a level 0), or
+// k_bytes_tree_digest's rule with the element read from the STAGED values
+// (vals + w * elem_len) instead of the element buffer, so a tree's digest
+// segment does not wait for its scatter segment of the same launch.  Every
+// thread writes only its own piece or digest: no counters, no hand-off.
+__global__ __launch_bounds__(256) void k_trees_stage0(Stage0Args g) {
+    const Stage0Seg& s = g.s[blockIdx.y];
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t T = s.k_idx + s.n_app;
+    if (s.mode >= kStage0Digest) {  // one thread per work item
+        const uint64_t w = gid;
+        if (w >= T) return;
+        uint64_t x;
+        if (w < s.k_idx) {
+            x = s.idx[w];
+            if (x >= s.n_old) return;
+        } else {
+            x = s.n_old + (w - s.k_idx);
+        }
+        uint32_t d[8];
+        if (s.mode == kStage0Digest32)
+            elem32_digest(reinterpret_cast<const uint4*>(s.vals) + 2 * w, d);
+        else
+            elem_digest_any(s.vals + w * (uint64_t)s.item_len, s.item_len, d);
+        uint4* digests = reinterpret_cast<uint4*>(s.dst);
+        digests[2 * x] = make_uint4(d[0], d[1], d[2], d[3]);
+        digests[2 * x + 1] = make_uint4(d[4], d[5], d[6], d[7]);
+        return;
+    }
+    const uint32_t unit = s.mode;  // 8 or 1
+    const uint32_t per = s.item_len / unit;
+    const uint64_t v = gid / per;
+    const uint32_t w = (uint32_t)(gid - v * per);
+    if (v >= T) return;
+    const uint64_t x = v < s.k_idx ? s.idx[v] : s.n_old + (v - s.k_idx);
+    if (v < s.k_idx && x >= s.n_old) return;
+    const uint64_t src = v * s.item_len + (uint64_t)w * unit, dst = x * s.item_len + (uint64_t)w * unit;
+    if (unit == 8)
+        *reinterpret_cast<uint64_t*>(s.dst + dst) = *reinterpret_cast<const uint64_t*>(s.vals + src);
+    else
+        s.dst[dst] = s.vals[src];
+}
+
 }  // namespace mk

@@ -216,4 +216,25 @@ __global__ void k_struct_tree_gather(const uint8_t* rec, const uint64_t* idx, ui
 __global__ void k_bytes_tree_digest(const uint8_t* elems, uint32_t elem_len, uint32_t fast32, const uint64_t* idx,
                                     uint64_t k_idx, uint64_t n_old, uint64_t n_app, uint4* digests);
 
+// stage 0 of several resident trees in one launch (tree_many_api.cpp): the segment descriptors by
+// value, 1.8 KB of kernel arguments.  Work item v of a segment is listed index idx[v] (v < k_idx,
+// skipped when >= n_old), then appended item n_old + (v - k_idx); its value is vals + v * item_len.
+constexpr uint32_t kStage0Digest = 0x100;    // mode: element digests (elem_digest_any)
+constexpr uint32_t kStage0Digest32 = 0x101;  // ... of 32-B elements at a 16-B aligned `vals` (elem32_digest)
+struct Stage0Seg {
+    uint8_t* dst;          // scatter: the item buffer (or level 0, item_len 32); digest: level 0
+    const uint8_t* vals;   // the staged values of the k_idx + n_app work items, in work-item order
+    const uint64_t* idx;
+    uint64_t k_idx, n_old, n_app;
+    uint32_t item_len;
+    uint32_t mode;         // 8 or 1: scatter in pieces of that many bytes, one per thread; kStage0Digest*
+};
+constexpr uint32_t kStage0SegsMax = 2 * kTreesMax;
+struct Stage0Args {
+    Stage0Seg s[kStage0SegsMax];  // segment blockIdx.y
+};
+// grid (blocks of the largest segment, nseg): slice y is k_list_tree_scatter or k_bytes_tree_digest
+// (from the staged values) over s[y]; a block beyond its segment's work returns at once
+__global__ void k_trees_stage0(Stage0Args g);
+
 }  // namespace mk

@@ -244,6 +244,30 @@ int tree_update(TreeHandle* t, const uint64_t* idx, const uint8_t* values, uint6
 int tree_append(TreeHandle* t, const uint8_t* values, uint64_t k);
 int tree_root(TreeHandle* t, uint8_t* root);
 int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out);
+// each kind's TreeKind and an empty handle of its type for tree_new (null: the allocation failed)
+const TreeKind& list_tree_kind();
+const TreeKind& struct_tree_kind();
+const TreeKind& bytes_tree_kind();
+TreeHandle* list_tree_handle();
+TreeHandle* struct_tree_handle(const StructTreeLayout& L);
+TreeHandle* bytes_tree_handle();
+// A tree of a set (tree_set_api.cpp) that does not climb at a flush: room for
+// new_cap items (>= t->cap; larger: the items moved), the staged values
+// (device: k_idx ascending indices, k_idx + n_new - n_old values) written
+// through, then the build of n_new items.  Enqueues on st under the caller's
+// lock with the device bound; t->count is the caller's to set.
+int tree_write_through_build(TreeHandle* t, uint64_t n_old, uint64_t n_new, uint64_t new_cap, const uint64_t* d_idx,
+                             uint64_t k_idx, const void* d_values, hipStream_t st);
+
+// ---- several trees in one call (tree_many_api.cpp) ------------------------------------------
+// mk_ssz_trees_update_workspace_bytes with its error, and mk_dev_ssz_trees_update
+// after bind_stream(): every check, then the launches on st
+int trees_update_workspace(const mk_tree_update* trees, uint32_t ntrees, uint64_t* bytes);
+int trees_update(const mk_tree_update* trees, uint32_t ntrees, void* d_container, uint32_t container_len,
+                 void* d_container_root32, void* d_ws, uint64_t ws_bytes, hipStream_t st);
+int struct_tree_stage0_roots(const StructTreeLayout& L, const void* d_records, uint64_t n_new, uint64_t T,
+                             const void* d_values, void* d_roots, void* d_scratch, const void** d_new_roots,
+                             hipStream_t st);
 
 // ---- multi-device (multi_api.cpp) ------------------------------------------------
 int host_merkle_multi(const uint8_t* items, uint64_t n, uint32_t item_len, int nshards, const int* devs_in,

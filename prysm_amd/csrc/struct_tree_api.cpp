@@ -177,6 +177,34 @@ int struct_tree_stage0(const StructTreeLayout& L, void* d_records, uint64_t n_ol
     TRY(struct_launch_roots(src, T, sp, msg, roots, st));
     return list_tree_scatter(d_roots, d_idx, k_idx, n_old, n_app, 32, roots, st);
 }
+
+// The struct-roots launch of struct_tree_stage0 alone, for the batched stage 0
+// of several trees (tree_many_api.cpp), which has scattered d_values (non-null)
+// into d_records on this stream and scatters the new roots itself: a list of
+// one chunk gets every root again straight into d_roots (*d_new_roots = null),
+// a longer one the roots of its T work items from d_values into the scratch
+// (*d_new_roots: T x 32 B in work-item order; null when T == 0).
+int struct_tree_stage0_roots(const StructTreeLayout& L, const void* d_records, uint64_t n_new, uint64_t T,
+                             const void* d_values, void* d_roots, void* d_scratch, const void** d_new_roots,
+                             hipStream_t st) {
+    const UpdateWs w = update_ws(L, T);
+    uint8_t* gath = (uint8_t*)d_scratch;
+    uint8_t* msg = gath + (w.msg - w.gath);
+    uint8_t* roots = gath + (w.roots - w.gath);
+    *d_new_roots = nullptr;
+    if (st_chunks(n_new) <= 1) return struct_launch_roots(d_records, n_new, L.sp, msg, d_roots, st);
+    if (T == 0) return MK_OK;
+    TRY(struct_launch_roots(d_values, T, L.sp, msg, roots, st));
+    *d_new_roots = roots;
+    return MK_OK;
+}
+
+TreeHandle* struct_tree_handle(const StructTreeLayout& L) {
+    auto* t = new (std::nothrow) mk_struct_list_tree();
+    if (t) t->L = L;
+    return t;
+}
+const TreeKind& struct_tree_kind() { return kStructKind; }
 }  // namespace mk::rt
 
 extern "C" {

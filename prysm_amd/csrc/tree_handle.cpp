@@ -158,6 +158,24 @@ int tree_append(TreeHandle* t, const uint8_t* values, uint64_t k) {
     return MK_OK;
 }
 
+int tree_write_through_build(TreeHandle* t, uint64_t n_old, uint64_t n_new, uint64_t new_cap, const uint64_t* d_idx,
+                             uint64_t k_idx, const void* d_values, hipStream_t st) {
+    const uint32_t L = t->item_len;
+    if (new_cap > t->cap) {  // as tree_append: the layout depends on the capacity
+        TRY(t->kind->check_shape(n_new, new_cap, L));
+        DevBuf ni;
+        TRY(grow(ni, new_cap * L + 16));
+        if (n_old) HIPCHK(hipMemcpyAsync(ni.p, t->items.p, n_old * L, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(t->items.p);
+        t->items = ni;
+        TRY(grow_levels(t, new_cap));
+        t->cap = new_cap;
+    }
+    TRY(list_tree_scatter(t->items.p, d_idx, k_idx, n_old, n_new - n_old, L, d_values, st));
+    return rebuild(t, n_new, st);
+}
+
 int tree_root(TreeHandle* t, uint8_t* root) {
     if (!t || !root) return fail(MK_EINVAL, "null pointer");
     std::lock_guard<std::mutex> tl(t->mu);

@@ -1,0 +1,361 @@
+// A set of device-resident trees behind one host handle (mk_tree_set,
+// DESIGN.md §5j): up to MK_TREES_MAX trees of the three kinds, each one a
+// TreeHandle (tree_handle.cpp), and the hash message of the struct that holds
+// them.  Changes are collected on the host (tree_set_plan.cpp); a root is one
+// upload, the update over all the trees (tree_many_api.cpp) and one 32-B
+// read-back.
+#include "runtime.hpp"
+#include "tree_set_plan.hpp"
+
+using namespace mk;
+using namespace mk::rt;
+namespace sp = mk::setplan;
+
+struct mk_tree_set {
+    struct Tree {
+        TreeHandle* h = nullptr;
+        uint32_t kind = 0, coff = MK_NO_CONTAINER;
+        std::vector<mk_field> fields;  // STRUCT
+    };
+    std::mutex mu;
+    int dev = -1;  // the call's device of mk_tree_set_new; -1: the device current when the first tree is added
+    uint32_t container_len = 0;
+    std::vector<uint8_t> msg;  // the struct's hash message: what put() wrote, zeros elsewhere
+    std::vector<Tree> trees;
+    std::vector<sp::Pending> pend;  // trees[i]'s
+    bool dirty = false;             // something changed since the last flush
+    sp::SetPlan plan;               // of the flush in flight
+    void* host = nullptr;           // pinned staging: the message, then every tree's indices and values
+    size_t host_cap = 0;
+    DevBuf stage, ws, croot;  // the staging buffer in HBM (the message at its front), workspace, container root
+};
+
+namespace {
+
+uint32_t nparts(const mk_tree_set* s) {
+    uint32_t n = 0;
+    for (const auto& t : s->trees) n += t.coff != MK_NO_CONTAINER;
+    return n;
+}
+
+int check_tree(const mk_tree_set* s, uint32_t tree) {
+    if (tree >= s->trees.size()) return fail(MK_EINVAL, "tree %u of a set of %zu", tree, s->trees.size());
+    return MK_OK;
+}
+
+// the set's device bound for this call (decided by the first call that needs one)
+int bind_set(mk_tree_set* s) {
+    if (s->dev >= 0) return bind_dev(s->dev);
+    TRY(bind_call());
+    s->dev = t_bound;
+    return MK_OK;
+}
+
+// Everything pending onto the device and every root brought up to date,
+// enqueued on the context's stream; the caller adds its read-back,
+// synchronises and calls flushed().  Nothing to do when nothing changed.
+int flush(mk_tree_set* s) {
+    if (!s->dirty || s->trees.empty()) return MK_OK;
+    const uint32_t nt = (uint32_t)s->trees.size();
+    hipStream_t st = ctx()->stream;
+    for (uint32_t i = 0; i < nt; ++i) s->pend[i].cap = s->trees[i].h->cap;
+    sp::make_plan(s->pend.data(), nt, (s->container_len + 15) & ~15u, s->plan);
+    const sp::SetPlan& P = s->plan;
+    if (s->host_cap < P.bytes) {
+        if (s->host) (void)hipHostFree(s->host);
+        s->host = nullptr;
+        s->host_cap = 0;
+        const size_t cap = std::max<size_t>(2 * P.bytes, 64 << 10);
+        if (hipHostMalloc(&s->host, cap, hipHostMallocDefault) != hipSuccess)
+            return fail(MK_ENOMEM, "hipHostMalloc(%zu) failed", cap);
+        s->host_cap = cap;
+    }
+    TRY(grow(s->stage, std::max<size_t>(s->host_cap, 16)));
+    TRY(grow(s->croot, 32));
+    uint8_t* host = (uint8_t*)s->host;
+    uint8_t* stage = (uint8_t*)s->stage.p;
+    if (s->container_len) std::memcpy(host, s->msg.data(), s->container_len);
+    sp::pack(s->pend.data(), nt, P, host);
+    if (P.bytes) HIPCHK(hipMemcpyAsync(stage, host, P.bytes, hipMemcpyHostToDevice, st));
+    mk_tree_update table[MK_TREES_MAX] = {};
+    for (uint32_t i = 0; i < nt; ++i) {
+        const mk_tree_set::Tree& t = s->trees[i];
+        const sp::TreePlan& p = P.tree[i];
+        const uint64_t* d_idx = (const uint64_t*)(stage + p.idx_off);
+        const uint8_t* d_vals = stage + p.val_off;
+        const uint64_t T = p.k_idx + (p.n_new - p.n_old);
+        mk_tree_update& u = table[i];
+        u.n_old = p.n_old;
+        u.n_new = p.n_new;
+        if (p.action != sp::kClimb) {  // built here: enters the update with nothing dirty
+            TRY(tree_write_through_build(t.h, p.n_old, p.n_new, p.new_cap, d_idx, p.k_idx, d_vals, st));
+            u.n_old = p.n_new;
+        } else if (T) {
+            u.d_idx = p.k_idx ? d_idx : nullptr;
+            u.k_idx = p.k_idx;
+            u.d_values = d_vals;
+        }
+        u.kind = t.kind;
+        u.item_len = t.h->item_len;
+        u.d_items = t.h->items.p;
+        u.d_level0 = t.h->level0.p;
+        u.d_levels = t.h->levels.p;
+        u.capacity = t.h->cap;
+        u.fields = t.fields.empty() ? nullptr : t.fields.data();
+        u.nfields = (uint32_t)t.fields.size();
+        u.container_off = t.coff;
+        u.d_root32 = t.h->root.p;
+    }
+    const uint32_t clen = nparts(s) ? s->container_len : 0;
+    uint64_t need = 0;
+    TRY(trees_update_workspace(table, nt, &need));
+    TRY(grow(s->ws, need));
+    return trees_update(table, nt, clen ? stage : nullptr, clen, clen ? s->croot.p : nullptr, s->ws.p, s->ws.cap, st);
+}
+
+// after the synchronise that followed flush(): the pending changes are the trees' content
+void flushed(mk_tree_set* s) {
+    if (!s->dirty || s->trees.empty()) return;
+    for (size_t i = 0; i < s->trees.size(); ++i) {
+        sp::commit(s->pend[i], s->plan.tree[i]);
+        s->pend[i].cap = s->trees[i].h->cap;
+        s->trees[i].h->count = s->pend[i].n;
+    }
+    s->dirty = false;
+}
+
+// flush, 32 bytes at d_src (looked up after the flush: a grown tree moved) to the host, one synchronise
+template <class Src>
+int flush_read32(mk_tree_set* s, const Src& d_src, uint8_t* out) {
+    TRY(bind_set(s));
+    TRY(flush(s));
+    hipStream_t st = ctx()->stream;
+    HIPCHK(hipMemcpyAsync(out, d_src(), 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    flushed(s);
+    return MK_OK;
+}
+
+int set_add(mk_tree_set* s, uint32_t kind, uint32_t item_len, const mk_field* fields, uint32_t nfields,
+            uint64_t capacity, uint32_t container_off, uint32_t* tree) {
+    if (!s || !tree) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->trees.size() >= MK_TREES_MAX) return fail(MK_EINVAL, "a set holds at most %d trees", MK_TREES_MAX);
+    const TreeKind* K = nullptr;
+    StructTreeLayout L;
+    if (kind == MK_TREE_LIST || kind == MK_TREE_BYTES) {
+        if (fields || nfields) return fail(MK_EINVAL, "a field layout for a tree of kind %u", kind);
+        K = kind == MK_TREE_LIST ? &list_tree_kind() : &bytes_tree_kind();
+    } else if (kind == MK_TREE_STRUCT) {
+        if (!fields || !nfields) return fail(MK_EINVAL, "a struct tree without its field layout");
+        TRY(struct_tree_layout(fields, nfields, item_len, L));
+        K = &struct_tree_kind();
+    } else {
+        return fail(MK_EINVAL, "unknown kind %u", kind);
+    }
+    TRY(K->check_shape(0, std::max<uint64_t>(capacity, 1), item_len));
+    if (container_off != MK_NO_CONTAINER) {
+        if (container_off % 4) return fail(MK_EINVAL, "container offset %u not 4-byte aligned", container_off);
+        if ((uint64_t)container_off + 32 > s->container_len)
+            return fail(MK_EINVAL, "root at offset %u beyond the %u-byte container", container_off, s->container_len);
+        for (size_t j = 0; j < s->trees.size(); ++j) {
+            const uint32_t o = s->trees[j].coff;
+            if (o != MK_NO_CONTAINER && container_off < o + 32 && o < container_off + 32)
+                return fail(MK_EINVAL, "the root overlaps tree %zu's in the container", j);
+        }
+    }
+    TRY(bind_set(s));
+    TreeHandle* h = kind == MK_TREE_LIST    ? list_tree_handle()
+                    : kind == MK_TREE_BYTES ? bytes_tree_handle()
+                                            : struct_tree_handle(L);
+    TRY(tree_new(h, *K, item_len, capacity));  // frees h on failure
+    mk_tree_set::Tree t;
+    t.h = h;
+    t.kind = kind;
+    t.coff = container_off;
+    if (fields) t.fields.assign(fields, fields + nfields);
+    sp::Pending p;
+    p.item_len = item_len;
+    p.rebuild_div = K->rebuild_div;
+    p.cap = h->cap;
+    s->trees.push_back(std::move(t));
+    s->pend.push_back(std::move(p));
+    s->dirty = true;  // its root is not in the message yet
+    *tree = (uint32_t)s->trees.size() - 1;
+    return MK_OK;
+}
+
+int set_put(mk_tree_set* s, uint32_t off, const uint8_t* bytes, uint32_t len) {
+    if (!s || (len && !bytes)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((uint64_t)off + len > s->container_len)
+        return fail(MK_EINVAL, "[%u, +%u) leaves the %u-byte container", off, len, s->container_len);
+    for (size_t j = 0; len && j < s->trees.size(); ++j) {
+        const uint32_t o = s->trees[j].coff;
+        if (o != MK_NO_CONTAINER && off < o + 32 && o < (uint64_t)off + len)
+            return fail(MK_EINVAL, "[%u, +%u) touches tree %zu's root at %u", off, len, j, o);
+    }
+    if (len) std::memcpy(s->msg.data() + off, bytes, len);
+    s->dirty = true;
+    return MK_OK;
+}
+
+int set_assign(mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t n) {
+    if (!s) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    TreeHandle* h = s->trees[tree].h;
+    TRY(tree_assign(h, values, n));
+    sp::record_assign(s->pend[tree], n, h->cap);
+    s->dirty = true;
+    return MK_OK;
+}
+
+int set_update(mk_tree_set* s, uint32_t tree, const uint64_t* idx, const uint8_t* values, uint64_t k) {
+    if (!s || (k && (!idx || !values))) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    const TreeHandle* h = s->trees[tree].h;
+    sp::Pending& p = s->pend[tree];
+    for (uint64_t i = 0; i < k; ++i)
+        if (idx[i] >= p.count())
+            return fail(MK_EINVAL, "index %llu beyond %llu %s", (unsigned long long)idx[i],
+                        (unsigned long long)p.count(), h->kind->noun);
+    if (k == 0) return MK_OK;
+    if (h->kind->check_values) TRY(h->kind->check_values(*h, values, k));
+    (void)sp::record_update(p, idx, values, k);
+    s->dirty = true;
+    return MK_OK;
+}
+
+int set_append(mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t k) {
+    if (!s || (k && !values)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    const TreeHandle* h = s->trees[tree].h;
+    sp::Pending& p = s->pend[tree];
+    if (k == 0) return MK_OK;
+    if (k >= kMaxWork || p.count() + k < k)
+        return fail(MK_EINVAL, "%llu %s in one append", (unsigned long long)k, h->kind->noun);
+    if (h->kind->check_values) TRY(h->kind->check_values(*h, values, k));
+    sp::record_append(p, values, k);
+    s->dirty = true;
+    return MK_OK;
+}
+
+int set_root(mk_tree_set* s, uint8_t* root) {
+    if (!s || !root) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->container_len == 0) return fail(MK_EINVAL, "a set without a container has no root");
+    if (nparts(s) == 0) return fail(MK_EINVAL, "a container no tree takes part in");
+    return flush_read32(s, [&] { return (const void*)s->croot.p; }, root);
+}
+
+int set_tree_root(mk_tree_set* s, uint32_t tree, uint8_t* root) {
+    if (!s || !root) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    return flush_read32(s, [&] { return (const void*)s->trees[tree].h->root.p; }, root);
+}
+
+int set_items(mk_tree_set* s, uint32_t tree, uint64_t first, uint64_t cnt, uint8_t* out) {
+    if (!s || (cnt && !out)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    const sp::Pending& p = s->pend[tree];
+    if (first > p.count() || cnt > p.count() - first)
+        return fail(MK_EINVAL, "[%llu, +%llu) beyond %llu %s", (unsigned long long)first, (unsigned long long)cnt,
+                    (unsigned long long)p.count(), s->trees[tree].h->kind->noun);
+    if (s->dirty) {
+        TRY(bind_set(s));
+        TRY(flush(s));
+        HIPCHK(hipStreamSynchronize(ctx()->stream));
+        flushed(s);
+    }
+    return tree_read(s->trees[tree].h, first, cnt, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+// No device is needed before the first tree is added: a bad argument is MK_EINVAL on any machine.
+int mk_tree_set_new(mk_call* call, uint32_t container_len, mk_tree_set** out) {
+    Scope S(call, false);
+    if (!out) return S.done(fail(MK_EINVAL, "null pointer"));
+    *out = nullptr;
+    if (container_len > MK_CONTAINER_MAX)
+        return S.done(fail(MK_EINVAL, "container of %u bytes (limit %d)", container_len, MK_CONTAINER_MAX));
+    auto* s = new (std::nothrow) mk_tree_set();
+    if (!s) return S.done(fail(MK_ENOMEM, "tree set allocation failed"));
+    s->dev = call ? call->device : -1;
+    s->container_len = container_len;
+    s->msg.assign(container_len, 0);
+    *out = s;
+    return S.done(MK_OK);
+}
+
+void mk_tree_set_free(mk_tree_set* s) {
+    if (!s) return;
+    for (auto& t : s->trees) tree_free(t.h);  // each restores the caller's device
+    if (s->dev >= 0 && (s->host || s->stage.p || s->ws.p || s->croot.p)) {
+        int saved = -1;
+        const bool restore = hipGetDevice(&saved) == hipSuccess;
+        (void)hipSetDevice(s->dev);
+        if (s->host) (void)hipHostFree(s->host);
+        for (DevBuf* b : {&s->stage, &s->ws, &s->croot})
+            if (b->p) (void)hipFree(b->p);
+        if (restore) (void)hipSetDevice(saved);
+    }
+    delete s;
+}
+
+int mk_tree_set_add(mk_call* call, mk_tree_set* s, uint32_t kind, uint32_t item_len, const mk_field* fields,
+                    uint32_t nfields, uint64_t capacity, uint32_t container_off, uint32_t* tree) {
+    Scope S(call);
+    return S.done(set_add(s, kind, item_len, fields, nfields, capacity, container_off, tree));
+}
+
+int mk_tree_set_put(mk_call* call, mk_tree_set* s, uint32_t off, const uint8_t* bytes, uint32_t len) {
+    Scope S(call, false);
+    return S.done(set_put(s, off, bytes, len));
+}
+
+int mk_tree_set_assign(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t n) {
+    Scope S(call);
+    return S.done(set_assign(s, tree, values, n));
+}
+
+int mk_tree_set_update(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, const uint8_t* values,
+                       uint64_t k) {
+    Scope S(call, false);
+    return S.done(set_update(s, tree, idx, values, k));
+}
+
+int mk_tree_set_append(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t k) {
+    Scope S(call, false);
+    return S.done(set_append(s, tree, values, k));
+}
+
+uint64_t mk_tree_set_count(const mk_tree_set* s, uint32_t tree) {
+    if (!s) return 0;
+    std::lock_guard<std::mutex> lk(const_cast<mk_tree_set*>(s)->mu);
+    return tree < s->pend.size() ? s->pend[tree].count() : 0;
+}
+
+int mk_tree_set_root(mk_call* call, mk_tree_set* s, uint8_t root[32]) {
+    Scope S(call);
+    return S.done(set_root(s, root));
+}
+
+int mk_tree_set_tree_root(mk_call* call, mk_tree_set* s, uint32_t tree, uint8_t root[32]) {
+    Scope S(call);
+    return S.done(set_tree_root(s, tree, root));
+}
+
+int mk_tree_set_items(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t first, uint64_t cnt, uint8_t* out) {
+    Scope S(call);
+    return S.done(set_items(s, tree, first, cnt, out));
+}
+
+}  // extern "C"

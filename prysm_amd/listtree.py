@@ -162,3 +162,121 @@ class BytesListTree(_Tree):
     def __init__(self, elem_len: int, capacity: int = 0, device: int = -1):
         super().__init__(elem_len, int(capacity), device=device)
         self.elem_len = self._len
+
+
+class TreeSet:
+    """Up to ``_lib.MK_TREES_MAX`` resident trees of the three kinds and the
+    hash message of the struct that holds them behind one handle
+    (``mk_tree_set_*``).  ``update`` / ``append`` / ``put`` only
+    record the change on the host; ``root()`` uploads every tree's changes in
+    one copy, runs the update over all the trees (every climb and the hash of
+    the message in one launch) and reads 32 bytes back::
+
+        s = TreeSet(container_len=72)
+        bal = s.add(_lib.MK_TREE_LIST, 8, container_off=0)
+        roots = s.add(_lib.MK_TREE_BYTES, 32, container_off=32)
+        s.put(64, slot_le64)                                      # the other fields
+        s.assign(bal, balances); s.assign(roots, block_roots)     # once
+        s.update(bal, [17], new_balance); s.append(roots, r)      # per slot
+        root = s.root()              # == TreeHash of the whole struct
+
+    numpy in, bytes out; there is no CPU fallback."""
+
+    def __init__(self, container_len: int = 0, device: int = -1):
+        self.container_len = int(container_len)
+        self._device = device
+        self._handle = None
+        self._len = []  # value length of every tree
+        h = ctypes.c_void_p()
+        _lib.invoke("mk_tree_set_new", self.container_len, ctypes.byref(h), device=device)
+        self._handle = h
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and _lib is not None:
+            try:
+                _lib.load().mk_tree_set_free(h)
+            except Exception:
+                pass
+
+    def __len__(self) -> int:
+        return len(self._len)
+
+    def _call(self, op: str, *args):
+        _lib.invoke(f"mk_tree_set_{op}", self._handle, *args, device=self._device)
+
+    def _tree(self, tree) -> int:
+        """The number of a tree (a subclass may know its trees by name)."""
+        return int(tree)
+
+    def _flat(self, tree: int, values) -> np.ndarray:
+        a = np.ascontiguousarray(values)
+        a = (a.view(np.uint8) if a.dtype != np.uint8 else a).reshape(-1)
+        L = self._len[tree]
+        if a.size % L:
+            raise ValueError(f"{a.size} bytes are not a whole number of {L}-byte values")
+        return a
+
+    def add(self, kind: int, value_len: int, fields=None, capacity: int = 0, container_off: int = None) -> int:
+        """A new, empty tree; returns its number.  ``fields``: the record
+        layout of a ``MK_TREE_STRUCT`` tree; ``container_off``: where its root
+        goes in the message (None: it is no field of it)."""
+        from .registry import _fields
+
+        out = ctypes.c_uint32()
+        off = _lib.MK_NO_CONTAINER if container_off is None else int(container_off)
+        spec = list(fields) if fields is not None else []
+        self._call("add", int(kind), int(value_len), _fields(spec) if fields is not None else None, len(spec),
+                   int(capacity), off, ctypes.byref(out))
+        self._len.append(int(value_len))
+        return int(out.value)
+
+    def put(self, off: int, data) -> None:
+        """Bytes of the message outside every tree's root: the other fields' outputs."""
+        a = np.frombuffer(bytes(data), dtype=np.uint8)
+        self._call("put", int(off), _ptr(a), a.size)
+
+    def assign(self, tree, values) -> None:
+        """Replace the whole list of a tree (through the build entry, at once)."""
+        tree = self._tree(tree)
+        a = self._flat(tree, values)
+        self._call("assign", tree, _ptr(a), a.size // self._len[tree])
+
+    def update(self, tree, indices, values) -> None:
+        """``list[indices[j]] = values[j]`` in order, recorded on the host; an
+        index >= count(tree) raises and changes nothing."""
+        tree = self._tree(tree)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        a = self._flat(tree, values)
+        if a.size != idx.size * self._len[tree]:
+            raise ValueError("one value per index")
+        self._call("update", tree, _ptr(idx), _ptr(a), idx.size)
+
+    def append(self, tree, values) -> None:
+        tree = self._tree(tree)
+        a = self._flat(tree, values)
+        self._call("append", tree, _ptr(a), a.size // self._len[tree])
+
+    def count(self, tree) -> int:
+        """Items of a tree, pending appends included."""
+        return int(_lib.load().mk_tree_set_count(self._handle, self._tree(tree)))
+
+    def root(self) -> bytes:
+        """The hash of the message with every tree's root in place."""
+        out = ctypes.create_string_buffer(32)
+        self._call("root", out)
+        return out.raw
+
+    def tree_root(self, tree) -> bytes:
+        out = ctypes.create_string_buffer(32)
+        self._call("tree_root", self._tree(tree), out)
+        return out.raw
+
+    def items(self, tree, first: int = 0, count: int = None) -> np.ndarray:
+        """Values [first, first + count) of a tree as a (count, value_len) uint8 array."""
+        tree = self._tree(tree)
+        if count is None:
+            count = self.count(tree) - first
+        out = np.empty((max(count, 0), self._len[tree]), dtype=np.uint8)
+        self._call("items", tree, first, count, _ptr(out))
+        return out

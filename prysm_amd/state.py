@@ -700,3 +700,79 @@ class ResidentBeaconState:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             D.trees_update(trees, self.container, CONTAINER_LEN, self.state_root, self._ws)
             return bytes(self.state_root.cpu().numpy())
+
+
+# ---------------------------------------------------------------- the resident state behind one C handle
+from .listtree import TreeSet  # noqa: E402
+
+
+class BeaconTreeSet(TreeSet):
+    """A ``listtree.TreeSet`` with the ten trees of ``RESIDENT_TREES`` at
+    ``CONTAINER_OFF`` in a ``CONTAINER_LEN`` message (``mk_tree_set``, DESIGN.md
+    §5j): what a cgo caller holds for a ``pb.BeaconState``.  A tree goes by its
+    number or its ``RESIDENT_TREES`` attribute name; values are packed rows as
+    for ``ResidentBeaconState`` (an ``Attestations`` is packed into 48-byte
+    bitfield slots)."""
+
+    def __init__(self, device: int = -1):
+        super().__init__(CONTAINER_LEN, device=device)
+        self.tree = {attr: self.add(kind, item_len, fields=spec, container_off=CONTAINER_OFF[field_name])
+                     for attr, field_name, kind, item_len, spec in RESIDENT_TREES}
+
+    def _tree(self, tree) -> int:
+        return self.tree[tree] if isinstance(tree, str) else int(tree)
+
+    def _flat(self, tree: int, values) -> np.ndarray:
+        if isinstance(values, Attestations):
+            values = pack_attestations(values, 48)[0]
+        return super()._flat(tree, values)
+
+    # ---- the small fields: their outputs into the message
+    def set_scalar(self, name: str, value: int) -> None:
+        if name not in _SCALARS:
+            raise KeyError(name)
+        self.put(CONTAINER_OFF[name], _st.pack("<Q", int(value)))
+
+    def set_seeds(self, previous: bytes, current: bytes) -> None:
+        msgs = np.empty((2, 36), dtype=np.uint8)
+        msgs[:, :4] = np.frombuffer(_st.pack("<I", 32), dtype=np.uint8)
+        msgs[0, 4:] = np.frombuffer(bytes(previous), dtype=np.uint8)
+        msgs[1, 4:] = np.frombuffer(bytes(current), dtype=np.uint8)
+        h = hash_batch(msgs, 36)
+        self.put(CONTAINER_OFF["PreviousEpochSeedHash32"], bytes(h[0]) + bytes(h[1]))
+
+    def set_eth1_data(self, eth1_data) -> None:
+        rec = np.ascontiguousarray(eth1_data, dtype=np.uint8).reshape(1, 64)
+        self.put(CONTAINER_OFF["LatestEth1Data"], bytes(struct_roots_packed(rec, ETH1_DATA_FIELDS)[0]))
+
+    def set_fork(self, fork) -> None:
+        msg = b"".join(_st.pack("<Q", int(x)) for x in fork)
+        self.put(CONTAINER_OFF["Fork"], hash_batch_var([msg])[0])
+
+    def assign_state(self, state: BeaconState) -> None:
+        """Every small field put, every list assigned from ``state``."""
+        for name in _SCALARS:
+            self.set_scalar(name, state.scalars[name])
+        self.set_seeds(bytes(state.seeds[0]), bytes(state.seeds[1]))
+        self.set_eth1_data(state.eth1_data)
+        self.set_fork(state.fork)
+        self.assign("registry", state.registry.records)
+        self.assign("balances", state.balances.astype("<u8"))
+        self.assign("randao_mixes", state.randao_mixes)
+        self.assign("crosslinks", pack_crosslinks(state.crosslink_epochs, state.crosslink_roots))
+        self.assign("latest_block_roots", state.latest_block_roots)
+        self.assign("batched_block_roots", state.batched_block_roots)
+        self.assign("penalized_balances", state.penalized_balances.astype("<u8"))
+        self.assign("attestations", state.attestations)
+        self.assign("index_roots", state.index_roots)
+        self.assign("eth1_votes", pack_eth1_votes(state.eth1_votes, state.eth1_vote_counts))
+
+
+def beacon_tree_set(state: BeaconState = None, device: int = -1) -> BeaconTreeSet:
+    """The tree set of a ``pb.BeaconState`` (filled from ``state`` when given):
+    ``root()`` is ssz.TreeHash of the state -- one upload, one update over the
+    ten trees, one 32-B read-back."""
+    s = BeaconTreeSet(device=device)
+    if state is not None:
+        s.assign_state(state)
+    return s
