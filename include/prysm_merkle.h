@@ -177,6 +177,30 @@ uint64_t mk_ssz_list_tree_update_workspace_bytes(uint64_t k);
 int mk_dev_ssz_list_tree_update(mk_call* call, void* d_items, uint64_t n_old, uint64_t n_new, uint64_t capacity,
                                 uint32_t item_len, void* d_levels, const uint64_t* d_idx, uint64_t k_idx,
                                 const void* d_values, void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream);
+/* Shrink on the device, one entry for both forms.
+ * Erase: d_rm holds k_rm > 0 strictly ascending item indices < n_old (device
+ * memory, 8-B aligned) that leave the list; the survivors close the gaps in
+ * order (a stable compaction) and n_new must be n_old - k_rm.  `first` is a
+ * host-side lower bound of the removed indices: items below it are not
+ * touched (0 is always allowed and only costs time), first <= n_new.
+ * Truncate: k_rm == 0 and n_new <= n_old given explicitly, the first n_new
+ * items stay (d_rm and first's value are unused, first <= n_new still holds).
+ * The items move inside d_items (through the workspace); the tree is climbed
+ * from the first moved item, or its levels rebuilt when that is cheaper;
+ * nodes to the right of the new end stay unspecified.  The root, with n_new
+ * mixed in, goes to d_root32.  Workspace (8-B aligned, 16 B lets 16-B items
+ * move in 16-B pieces) from mk_ssz_list_tree_erase_workspace_bytes(moved,
+ * item_len), moved = n_new - first for an erase (< 2^31) and 0 for a
+ * truncate; 0 for item_len == 0 or moved >= 2^31.  Every argument is checked
+ * before a device is looked up: null or misaligned pointers, n_new > n_old,
+ * k_rm > n_old, n_new != n_old - k_rm, first > n_new are MK_EINVAL, a short
+ * workspace MK_ENOMEM.  A list that is not ascending gives an undefined list
+ * and root but no access outside the buffers.  Allocates nothing: capturable
+ * into a hipGraph.  mk_dev_ssz_list_tree_update still rejects n_new < n_old. */
+uint64_t mk_ssz_list_tree_erase_workspace_bytes(uint64_t moved, uint32_t item_len);
+int mk_dev_ssz_list_tree_erase(mk_call* call, void* d_items, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                               uint32_t item_len, void* d_levels, const uint64_t* d_rm, uint64_t k_rm, uint64_t first,
+                               void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream);
 /* Handle form for host callers: items and levels stay in HBM under a
  * per-handle lock (the validator registry's roots, the balances).  update
  * takes host indices in any order (list[idx[j]] = values[j] in sequence: of a
@@ -193,6 +217,13 @@ uint64_t mk_list_tree_count(const mk_list_tree* t);
 int mk_list_tree_assign(mk_call* call, mk_list_tree* t, const uint8_t* items, uint64_t n);
 int mk_list_tree_update(mk_call* call, mk_list_tree* t, const uint64_t* idx, const uint8_t* values, uint64_t k);
 int mk_list_tree_append(mk_call* call, mk_list_tree* t, const uint8_t* items, uint64_t k);
+/* Shrink without giving the residency up: truncate keeps the first n items
+ * (n > count is MK_EINVAL, n == count a no-op); erase removes the items at the
+ * k host indices (any order, a repeated index counts once; an index >= count
+ * is MK_EINVAL and nothing changes; k == 0 a no-op) and closes the gaps in
+ * order.  Only the sorted indices are uploaded; capacity and buffers stay. */
+int mk_list_tree_truncate(mk_call* call, mk_list_tree* t, uint64_t n);
+int mk_list_tree_erase(mk_call* call, mk_list_tree* t, const uint64_t* idx, uint64_t k);
 int mk_list_tree_root(mk_call* call, mk_list_tree* t, uint8_t root[32]);
 /* Items [first, first + cnt), cnt x item_len bytes. */
 int mk_list_tree_items(mk_call* call, mk_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
@@ -473,6 +504,19 @@ int mk_dev_ssz_struct_list_tree_update(mk_call* call, void* d_records, uint64_t 
                                        uint32_t nfields, void* d_roots, void* d_levels, const uint64_t* d_idx,
                                        uint64_t k_idx, const void* d_values, void* d_root32, void* d_ws,
                                        uint64_t ws_bytes, void* stream);
+/* Shrink on the device, mk_dev_ssz_list_tree_erase's contract
+ * with records for items: the records AND their 32-B struct roots in d_roots
+ * move, no record is hashed again; k_rm == 0 with n_new <= n_old is the
+ * truncate.  Workspace from mk_ssz_struct_list_tree_erase_workspace_bytes(
+ * moved, record_len), moved = n_new - first (0 for a truncate).  Besides the
+ * list tree's checks a bad field layout is MK_EINVAL; all of them come before
+ * any device lookup.  Allocates nothing and can be captured into a hipGraph. */
+uint64_t mk_ssz_struct_list_tree_erase_workspace_bytes(uint64_t moved, uint32_t record_len);
+int mk_dev_ssz_struct_list_tree_erase(mk_call* call, void* d_records, uint64_t n_old, uint64_t n_new,
+                                      uint64_t capacity, uint32_t record_len, const mk_field* fields,
+                                      uint32_t nfields, void* d_roots, void* d_levels, const uint64_t* d_rm,
+                                      uint64_t k_rm, uint64_t first, void* d_root32, void* d_ws, uint64_t ws_bytes,
+                                      void* stream);
 /* Handle form for host callers (the validator registry): records, roots and
  * levels stay in HBM under a per-handle lock, with mk_list_tree's semantics.
  * update takes host indices in any order (list[idx[j]] = records[j] in
@@ -491,6 +535,9 @@ int mk_struct_list_tree_assign(mk_call* call, mk_struct_list_tree* t, const uint
 int mk_struct_list_tree_update(mk_call* call, mk_struct_list_tree* t, const uint64_t* idx, const uint8_t* records,
                                uint64_t k);
 int mk_struct_list_tree_append(mk_call* call, mk_struct_list_tree* t, const uint8_t* records, uint64_t k);
+/* mk_list_tree_truncate / _erase for records (CleanupAttestations' stable filter). */
+int mk_struct_list_tree_truncate(mk_call* call, mk_struct_list_tree* t, uint64_t n);
+int mk_struct_list_tree_erase(mk_call* call, mk_struct_list_tree* t, const uint64_t* idx, uint64_t k);
 int mk_struct_list_tree_root(mk_call* call, mk_struct_list_tree* t, uint8_t root[32]);
 /* Records [first, first + cnt), cnt x record_len bytes. */
 int mk_struct_list_tree_records(mk_call* call, mk_struct_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
@@ -540,6 +587,17 @@ int mk_dev_ssz_bytes_list_tree_update(mk_call* call, void* d_elems, uint64_t n_o
                                       uint32_t elem_len, void* d_digests, void* d_levels, const uint64_t* d_idx,
                                       uint64_t k_idx, const void* d_values, void* d_root32, void* d_ws,
                                       uint64_t ws_bytes, void* stream);
+/* Shrink on the device, mk_dev_ssz_list_tree_erase's contract
+ * with elements for items: the elements AND their digests in d_digests move,
+ * no element is digested again; k_rm == 0 with n_new <= n_old is the truncate.
+ * Workspace from mk_ssz_bytes_list_tree_erase_workspace_bytes(moved, elem_len),
+ * moved = n_new - first (0 for a truncate).  Every check comes before any
+ * device lookup.  Allocates nothing and can be captured into a hipGraph. */
+uint64_t mk_ssz_bytes_list_tree_erase_workspace_bytes(uint64_t moved, uint32_t elem_len);
+int mk_dev_ssz_bytes_list_tree_erase(mk_call* call, void* d_elems, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                                     uint32_t elem_len, void* d_digests, void* d_levels, const uint64_t* d_rm,
+                                     uint64_t k_rm, uint64_t first, void* d_root32, void* d_ws, uint64_t ws_bytes,
+                                     void* stream);
 /* Handle form for host callers (the state's root arrays): elements, digests
  * and levels stay in HBM under a per-handle lock, with mk_struct_list_tree's
  * semantics.  update takes host indices in any order (list[idx[j]] = elems[j]
@@ -557,6 +615,9 @@ int mk_bytes_list_tree_assign(mk_call* call, mk_bytes_list_tree* t, const uint8_
 int mk_bytes_list_tree_update(mk_call* call, mk_bytes_list_tree* t, const uint64_t* idx, const uint8_t* elems,
                               uint64_t k);
 int mk_bytes_list_tree_append(mk_call* call, mk_bytes_list_tree* t, const uint8_t* elems, uint64_t k);
+/* mk_list_tree_truncate / _erase for elements. */
+int mk_bytes_list_tree_truncate(mk_call* call, mk_bytes_list_tree* t, uint64_t n);
+int mk_bytes_list_tree_erase(mk_call* call, mk_bytes_list_tree* t, const uint64_t* idx, uint64_t k);
 int mk_bytes_list_tree_root(mk_call* call, mk_bytes_list_tree* t, uint8_t root[32]);
 /* Elements [first, first + cnt), cnt x elem_len bytes. */
 int mk_bytes_list_tree_elems(mk_call* call, mk_bytes_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
@@ -682,6 +743,13 @@ int mk_tree_set_assign(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8
 int mk_tree_set_update(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, const uint8_t* values,
                        uint64_t k);
 int mk_tree_set_append(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t k);
+/* Shrink one tree of the set, mk_list_tree_truncate / _erase
+ * against count(tree), pending appends included.  A shrink is not recorded:
+ * it first flushes whatever the set has pending, then shrinks that tree on
+ * the device at once; the next root carries its new root.  A failed shrink
+ * leaves the set as the flush left it; a bad argument changes nothing. */
+int mk_tree_set_truncate(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t n);
+int mk_tree_set_erase(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k);
 uint64_t mk_tree_set_count(const mk_tree_set* s, uint32_t tree);
 int mk_tree_set_root(mk_call* call, mk_tree_set* s, uint8_t root[32]);
 int mk_tree_set_tree_root(mk_call* call, mk_tree_set* s, uint32_t tree, uint8_t root[32]);

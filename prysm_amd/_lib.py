@@ -122,12 +122,17 @@ _SIGS = {
     "mk_ssz_list_tree_update_workspace_bytes": (_u64, [_u64]),
     "mk_dev_ssz_list_tree_update": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
                                            _vp]),
+    "mk_ssz_list_tree_erase_workspace_bytes": (_u64, [_u64, _u32]),
+    "mk_dev_ssz_list_tree_erase": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _vp, _u64, _u64, _vp, _vp, _u64,
+                                          _vp]),
     "mk_list_tree_new": (_int, [_cp, _u32, _u64, _vp]),
     "mk_list_tree_free": (None, [_vp]),
     "mk_list_tree_count": (_u64, [_vp]),
     "mk_list_tree_assign": (_int, [_cp, _vp, _vp, _u64]),
     "mk_list_tree_update": (_int, [_cp, _vp, _vp, _vp, _u64]),
     "mk_list_tree_append": (_int, [_cp, _vp, _vp, _u64]),
+    "mk_list_tree_truncate": (_int, [_cp, _vp, _u64]),
+    "mk_list_tree_erase": (_int, [_cp, _vp, _vp, _u64]),
     "mk_list_tree_root": (_int, [_cp, _vp, _vp]),
     "mk_list_tree_items": (_int, [_cp, _vp, _u64, _u64, _vp]),
     "mk_ssz_struct_list_tree_build_workspace_bytes": (_u64, [_u64, _vp, _u32]),
@@ -136,12 +141,17 @@ _SIGS = {
     "mk_ssz_struct_list_tree_update_workspace_bytes": (_u64, [_u64, _vp, _u32]),
     "mk_dev_ssz_struct_list_tree_update": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _vp, _u64,
                                                   _vp, _vp, _vp, _u64, _vp]),
+    "mk_ssz_struct_list_tree_erase_workspace_bytes": (_u64, [_u64, _u32]),
+    "mk_dev_ssz_struct_list_tree_erase": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _vp, _u64,
+                                                 _u64, _vp, _vp, _u64, _vp]),
     "mk_struct_list_tree_new": (_int, [_cp, _u32, _vp, _u32, _u64, _vp]),
     "mk_struct_list_tree_free": (None, [_vp]),
     "mk_struct_list_tree_count": (_u64, [_vp]),
     "mk_struct_list_tree_assign": (_int, [_cp, _vp, _vp, _u64]),
     "mk_struct_list_tree_update": (_int, [_cp, _vp, _vp, _vp, _u64]),
     "mk_struct_list_tree_append": (_int, [_cp, _vp, _vp, _u64]),
+    "mk_struct_list_tree_truncate": (_int, [_cp, _vp, _u64]),
+    "mk_struct_list_tree_erase": (_int, [_cp, _vp, _vp, _u64]),
     "mk_struct_list_tree_root": (_int, [_cp, _vp, _vp]),
     "mk_struct_list_tree_records": (_int, [_cp, _vp, _u64, _u64, _vp]),
     "mk_ssz_bytes_list_tree_build_workspace_bytes": (_u64, [_u64, _u32]),
@@ -149,12 +159,17 @@ _SIGS = {
     "mk_ssz_bytes_list_tree_update_workspace_bytes": (_u64, [_u64, _u32]),
     "mk_dev_ssz_bytes_list_tree_update": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp,
                                                  _vp, _u64, _vp]),
+    "mk_ssz_bytes_list_tree_erase_workspace_bytes": (_u64, [_u64, _u32]),
+    "mk_dev_ssz_bytes_list_tree_erase": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _u64, _vp,
+                                                _vp, _u64, _vp]),
     "mk_bytes_list_tree_new": (_int, [_cp, _u32, _u64, _vp]),
     "mk_bytes_list_tree_free": (None, [_vp]),
     "mk_bytes_list_tree_count": (_u64, [_vp]),
     "mk_bytes_list_tree_assign": (_int, [_cp, _vp, _vp, _u64]),
     "mk_bytes_list_tree_update": (_int, [_cp, _vp, _vp, _vp, _u64]),
     "mk_bytes_list_tree_append": (_int, [_cp, _vp, _vp, _u64]),
+    "mk_bytes_list_tree_truncate": (_int, [_cp, _vp, _u64]),
+    "mk_bytes_list_tree_erase": (_int, [_cp, _vp, _vp, _u64]),
     "mk_bytes_list_tree_root": (_int, [_cp, _vp, _vp]),
     "mk_bytes_list_tree_elems": (_int, [_cp, _vp, _u64, _u64, _vp]),
     "mk_ssz_trees_update_workspace_bytes": (_u64, [_vp, _u32]),
@@ -166,6 +181,8 @@ _SIGS = {
     "mk_tree_set_assign": (_int, [_cp, _vp, _u32, _vp, _u64]),
     "mk_tree_set_update": (_int, [_cp, _vp, _u32, _vp, _vp, _u64]),
     "mk_tree_set_append": (_int, [_cp, _vp, _u32, _vp, _u64]),
+    "mk_tree_set_truncate": (_int, [_cp, _vp, _u32, _u64]),
+    "mk_tree_set_erase": (_int, [_cp, _vp, _u32, _vp, _u64]),
     "mk_tree_set_count": (_u64, [_vp, _u32]),
     "mk_tree_set_root": (_int, [_cp, _vp, _vp]),
     "mk_tree_set_tree_root": (_int, [_cp, _vp, _u32, _vp]),

@@ -165,6 +165,27 @@ int mk_dev_ssz_bytes_list_tree_update(mk_call* call, void* d_elems, uint64_t n_o
     return S.done(rc);
 }
 
+uint64_t mk_ssz_bytes_list_tree_erase_workspace_bytes(uint64_t moved, uint32_t elem_len) {
+    return tree_shrink_ws(kBytesKind, moved, elem_len);
+}
+
+// The elements and their digests move; no element is digested.  Every
+// argument check comes before the stream's device is looked up.
+int mk_dev_ssz_bytes_list_tree_erase(mk_call* call, void* d_elems, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                                     uint32_t elem_len, void* d_digests, void* d_levels, const uint64_t* d_rm,
+                                     uint64_t k_rm, uint64_t first, void* d_root32, void* d_ws, uint64_t ws_bytes,
+                                     void* stream) {
+    Scope S(call);
+    int rc = tree_shrink_check(kBytesKind, n_old, n_new, capacity, elem_len, k_rm, first, ws_bytes);
+    if (!rc) rc = bytes_tree_check_ptrs(d_elems, n_old, capacity, d_digests, d_levels, d_root32, d_ws);
+    if (!rc && k_rm && (!d_rm || ((uintptr_t)d_rm % 8))) rc = fail(MK_EINVAL, "null or misaligned index array");
+    if (!rc) rc = bind_stream((hipStream_t)stream);
+    if (!rc)
+        rc = tree_shrink(kBytesKind, d_elems, elem_len, d_digests, d_levels, n_old, n_new, capacity, d_rm, k_rm, first,
+                         d_root32, d_ws, (hipStream_t)stream);
+    return S.done(rc);
+}
+
 int mk_bytes_list_tree_new(mk_call* call, uint32_t elem_len, uint64_t capacity, mk_bytes_list_tree** out) {
     Scope S(call);
     if (!out) return S.done(fail(MK_EINVAL, "null pointer"));
@@ -196,6 +217,16 @@ int mk_bytes_list_tree_update(mk_call* call, mk_bytes_list_tree* t, const uint64
 int mk_bytes_list_tree_append(mk_call* call, mk_bytes_list_tree* t, const uint8_t* elems, uint64_t k) {
     Scope S(call);
     return S.done(tree_append(t, elems, k));
+}
+
+int mk_bytes_list_tree_truncate(mk_call* call, mk_bytes_list_tree* t, uint64_t n) {
+    Scope S(call);
+    return S.done(tree_truncate(t, n));
+}
+
+int mk_bytes_list_tree_erase(mk_call* call, mk_bytes_list_tree* t, const uint64_t* idx, uint64_t k) {
+    Scope S(call);
+    return S.done(tree_erase(t, idx, k));
 }
 
 int mk_bytes_list_tree_root(mk_call* call, mk_bytes_list_tree* t, uint8_t root[32]) {

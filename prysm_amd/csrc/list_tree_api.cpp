@@ -179,6 +179,115 @@ mk::ListTreeArgs list_tree_args(const void* d_items, void* d_levels, const uint6
 
 TreeHandle* list_tree_handle() { return new (std::nothrow) mk_list_tree(); }
 const TreeKind& list_tree_kind() { return kListKind; }
+
+// ---- shrinking a resident tree of any kind ------------------------------------
+// A shrink rebuilds the levels (from level 0, never from the records) instead
+// of climbing when n_new / MK_TREE_SHRINK_REBUILD_DIV <= dirty, dirty the
+// suffix [first, n_new).  Its climb has no stage 0 and its dirty values are
+// one suffix that shares its ancestors, so the kinds' own divisors (512, 32,
+// 256: random indices, stage 0 included) are not its break-even: on 2^20 x
+// 32-B items the climb over a suffix of 2^14 costs 0.312 ms, the level build
+// 0.340 ms, a suffix of 2^16 0.573 ms -- a dirty share of 2^14 / 2^20 = 1/64,
+// the same for the three kinds, whose levels are this one tree
+// (tools/tree_shrink_probe.py, profiles/tree_shrink/probe.json).
+#define MK_TREE_SHRINK_REBUILD_DIV 64
+// Regions of the erase workspace for `moved` values: the climb's arrival words
+// (at most max(moved, 1) work items), the moved values, the moved level 0.
+namespace {
+struct ShrinkWs {
+    uint64_t vals, l0, total;
+};
+ShrinkWs shrink_ws(uint64_t moved, uint32_t item_len, bool level0) {
+    ShrinkWs w{};
+    w.vals = lt_update_ws(moved);
+    w.l0 = w.vals + align256(moved * item_len);
+    w.total = w.l0 + (level0 ? align256(32 * moved) : 0);
+    return w;
+}
+uint32_t compact_unit(uint32_t item_len, const void* a, const void* b) {
+    for (uint32_t u : {16u, 8u, 4u})
+        if (item_len % u == 0 && ((uintptr_t)a % u) == 0 && ((uintptr_t)b % u) == 0) return u;
+    return 1;
+}
+}  // namespace
+
+uint64_t tree_shrink_ws(const TreeKind& K, uint64_t moved, uint32_t item_len) {
+    if (item_len == 0 || moved >= kMaxWork) return 0;
+    return shrink_ws(moved, item_len, K.level0).total;
+}
+
+int tree_shrink_check(const TreeKind& K, uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len,
+                      uint64_t k_rm, uint64_t first, uint64_t ws_bytes) {
+    TRY(K.check_shape(n_old, capacity, item_len));
+    if (k_rm > n_old)
+        return fail(MK_EINVAL, "%llu removed indices of %llu %s", (unsigned long long)k_rm, (unsigned long long)n_old,
+                    K.noun);
+    if (n_new > n_old)
+        return fail(MK_EINVAL, "n_new %llu > n_old %llu (an erase does not grow the list)", (unsigned long long)n_new,
+                    (unsigned long long)n_old);
+    if (k_rm && n_new != n_old - k_rm)
+        return fail(MK_EINVAL, "n_new %llu is not n_old %llu less the %llu removed %s", (unsigned long long)n_new,
+                    (unsigned long long)n_old, (unsigned long long)k_rm, K.noun);
+    if (first > n_new)
+        return fail(MK_EINVAL, "first %llu beyond the %llu %s that stay", (unsigned long long)first,
+                    (unsigned long long)n_new, K.noun);
+    const uint64_t moved = k_rm ? n_new - first : 0;
+    if (moved >= kMaxWork)
+        return fail(MK_EINVAL, "%llu %s to move in one call (limit 2^31 - 1)", (unsigned long long)moved, K.noun);
+    if (ceil_div(moved * std::max<uint32_t>(item_len, 32), 256) >= kMaxWork)
+        return fail(MK_EINVAL, "%llu %s of %u bytes to move in one call", (unsigned long long)moved, K.noun, item_len);
+    if (ws_bytes < shrink_ws(moved, item_len, K.level0).total) return fail(MK_ENOMEM, "workspace too small");
+    return MK_OK;
+}
+
+// Values [first, n_new) and their level-0 entries take the survivors' (out of
+// place into the workspace, then back: a destination below its source may be
+// another block's source), then the tree over level 0 as it stands: nothing of
+// a survivor is hashed again.  The climb needs no index list: the dirty values
+// are the suffix [from, n_new), which lt_update takes as appended ones, and
+// every count, pad and the top level come from n_new alone, so the stale nodes
+// to the right of the new end are never read (§5k).
+int tree_shrink(const TreeKind& K, void* d_items, uint32_t item_len, void* d_level0, void* d_levels, uint64_t n_old,
+                uint64_t n_new, uint64_t capacity, const uint64_t* d_rm, uint64_t k_rm, uint64_t first,
+                void* d_root32, void* d_ws, hipStream_t st) {
+    (void)n_old;
+    const uint64_t moved = k_rm ? n_new - first : 0;
+    if (moved) {
+        const ShrinkWs w = shrink_ws(moved, item_len, K.level0);
+        uint8_t* items = (uint8_t*)d_items + first * item_len;
+        uint8_t* l0 = K.level0 ? (uint8_t*)d_level0 + 32 * first : nullptr;
+        uint8_t* wv = (uint8_t*)d_ws + w.vals;
+        uint8_t* wl = (uint8_t*)d_ws + w.l0;
+        mk::CompactArgs a{};
+        a.s[0] = {items, wv, item_len, compact_unit(item_len, items, wv)};
+        a.s[1] = {l0, wl, 32, compact_unit(32, l0, wl)};
+        a.rm = d_rm;
+        a.k_rm = k_rm;
+        a.first = first;
+        a.moved = moved;
+        const uint64_t p0 = moved * (item_len / a.s[0].unit), p1 = K.level0 ? moved * (32 / a.s[1].unit) : 0;
+        const dim3 grid((uint32_t)ceil_div(std::max(p0, p1), 256), K.level0 ? 2 : 1);
+        hipLaunchKernelGGL(mk::k_tree_compact, grid, dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        a.s[0].src = wv, a.s[0].dst = items;  // the moved range back in place
+        a.s[1].src = wl, a.s[1].dst = l0;
+        a.k_rm = 0;
+        hipLaunchKernelGGL(mk::k_tree_compact, grid, dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+    }
+    const void* leaves = K.level0 ? d_level0 : d_items;
+    const uint32_t leaf_len = K.level0 ? 32 : item_len;
+    if (lt_chunks(n_new, leaf_len) <= 1) {  // no levels: the mix-in over the raw chunk (0^128 when empty)
+        hipLaunchKernelGGL(mk::k_final_small, dim3(1), dim3(64), 0, st, (const uint8_t*)leaves, n_new * leaf_len,
+                           n_new, (uint8_t*)d_root32);
+        return launched();
+    }
+    // a truncate: the last value that stays is dirty, as the build's right edge
+    const uint64_t from = k_rm ? std::min(first, n_new - 1) : n_new - 1;
+    if (n_new / MK_TREE_SHRINK_REBUILD_DIV <= n_new - from)  // the climb does not pay: every level, from level 0
+        return dev_build(leaves, n_new, capacity, leaf_len, d_levels, d_root32, d_ws, st);
+    return launch_update(leaves, d_levels, nullptr, 0, from, n_new, capacity, leaf_len, d_root32, d_ws, st);
+}
 }  // namespace mk::rt
 
 extern "C" {
@@ -223,6 +332,25 @@ int mk_dev_ssz_list_tree_update(mk_call* call, void* d_items, uint64_t n_old, ui
     return S.done(rc);
 }
 
+uint64_t mk_ssz_list_tree_erase_workspace_bytes(uint64_t moved, uint32_t item_len) {
+    return tree_shrink_ws(kListKind, moved, item_len);
+}
+
+// Every argument check comes before the stream's device is looked up.
+int mk_dev_ssz_list_tree_erase(mk_call* call, void* d_items, uint64_t n_old, uint64_t n_new, uint64_t capacity,
+                               uint32_t item_len, void* d_levels, const uint64_t* d_rm, uint64_t k_rm, uint64_t first,
+                               void* d_root32, void* d_ws, uint64_t ws_bytes, void* stream) {
+    Scope S(call);
+    int rc = tree_shrink_check(kListKind, n_old, n_new, capacity, item_len, k_rm, first, ws_bytes);
+    if (!rc) rc = list_tree_check_ptrs(d_items, n_old, capacity, item_len, d_levels, d_root32, d_ws);
+    if (!rc && k_rm && (!d_rm || ((uintptr_t)d_rm % 8))) rc = fail(MK_EINVAL, "null or misaligned index array");
+    if (!rc) rc = bind_stream((hipStream_t)stream);
+    if (!rc)
+        rc = tree_shrink(kListKind, d_items, item_len, nullptr, d_levels, n_old, n_new, capacity, d_rm, k_rm, first,
+                         d_root32, d_ws, (hipStream_t)stream);
+    return S.done(rc);
+}
+
 int mk_list_tree_new(mk_call* call, uint32_t item_len, uint64_t capacity, mk_list_tree** out) {
     Scope S(call);
     if (!out) return S.done(fail(MK_EINVAL, "null pointer"));
@@ -253,6 +381,16 @@ int mk_list_tree_update(mk_call* call, mk_list_tree* t, const uint64_t* idx, con
 int mk_list_tree_append(mk_call* call, mk_list_tree* t, const uint8_t* items, uint64_t k) {
     Scope S(call);
     return S.done(tree_append(t, items, k));
+}
+
+int mk_list_tree_truncate(mk_call* call, mk_list_tree* t, uint64_t n) {
+    Scope S(call);
+    return S.done(tree_truncate(t, n));
+}
+
+int mk_list_tree_erase(mk_call* call, mk_list_tree* t, const uint64_t* idx, uint64_t k) {
+    Scope S(call);
+    return S.done(tree_erase(t, idx, k));
 }
 
 int mk_list_tree_root(mk_call* call, mk_list_tree* t, uint8_t root[32]) {

@@ -20,6 +20,7 @@
 
 #include "keccak_dev.hpp"
 #include "merkle_kernels.hpp"
+#include "tree_compact.hpp"
 
 namespace mk {
 
@@ -4759,6 +4760,47 @@ __global__ __launch_bounds__(256) void k_trees_stage0(Stage0Args g) {
         *reinterpret_cast<uint64_t*>(s.dst + dst) = *reinterpret_cast<const uint64_t*>(s.vals + src);
     else
         s.dst[dst] = s.vals[src];
+}
+
+// ----------------------------------------------------------------------------
+// Stable erase of a resident tree, gather form: one thread per
+// `unit`-byte piece of a destination value in [first, first + moved); segment
+// blockIdx.y is the value buffer or level 0.  Destination q reads source
+// q + j, j from the index map of tree_compact.hpp.  A block searches the whole
+// removal list twice -- for its first and its last destination -- and every
+// thread then bisects between the two, which for all but the blocks that span
+// a removed run is no step at all.  Out of place: dst never overlaps a source,
+// so every thread writes only its own piece: no counters, no hand-off.  With
+// k_rm == 0 (j == 0) it is the copy that puts the moved range back.
+__global__ __launch_bounds__(256) void k_tree_compact(CompactArgs g) {
+    const CompactSeg& s = g.s[blockIdx.y];
+    const uint32_t per = s.item_len / s.unit;
+    const uint64_t pieces = g.moved * per;
+    const uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x;
+    if (g0 >= pieces) return;  // the whole block: the other segment is the larger one
+    __shared__ uint64_t jb[2];
+    if (g.k_rm) {  // uniform over the launch
+        if (threadIdx.x < 2) {
+            const uint64_t last = g0 + blockDim.x - 1 < pieces ? g0 + blockDim.x - 1 : pieces - 1;
+            jb[threadIdx.x] = compact_skip(g.rm, g.k_rm, g.first + (threadIdx.x ? last : g0) / per);
+        }
+        __syncthreads();
+    }
+    const uint64_t gid = g0 + threadIdx.x;
+    if (gid >= pieces) return;
+    const uint64_t v = gid / per;
+    const uint32_t w = (uint32_t)(gid - v * per);
+    const uint64_t j = g.k_rm ? compact_skip_in(g.rm, jb[0], jb[1], g.first + v) : 0;  // <= k_rm for any list
+    const uint8_t* src = s.src + (v + j) * s.item_len + (uint64_t)w * s.unit;
+    uint8_t* dst = s.dst + v * s.item_len + (uint64_t)w * s.unit;
+    if (s.unit == 16)
+        *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+    else if (s.unit == 8)
+        *reinterpret_cast<uint64_t*>(dst) = *reinterpret_cast<const uint64_t*>(src);
+    else if (s.unit == 4)
+        *reinterpret_cast<uint32_t*>(dst) = *reinterpret_cast<const uint32_t*>(src);
+    else
+        *dst = *src;
 }
 
 }  // namespace mk

@@ -237,4 +237,21 @@ struct Stage0Args {
 // (from the staged values) over s[y]; a block beyond its segment's work returns at once
 __global__ void k_trees_stage0(Stage0Args g);
 
+// stable erase of a resident tree (list_tree_api.cpp): destinations [first, first +
+// moved) of a list gathered out of place, destination q from source q + j (tree_compact.hpp).  A
+// segment is one array that moves that way: the value buffer, and level 0 of a struct / bytes tree.
+struct CompactSeg {
+    const uint8_t* src;  // the value at position `first` of the source array
+    uint8_t* dst;        // where destination `first` goes (no overlap with any segment's source)
+    uint32_t item_len;
+    uint32_t unit;       // 16, 8, 4 or 1: bytes per thread; divides item_len and both addresses
+};
+struct CompactArgs {
+    CompactSeg s[2];     // segment blockIdx.y
+    const uint64_t* rm;  // k_rm strictly ascending removed indices (device); k_rm == 0: a plain copy
+    uint64_t k_rm, first, moved;
+};
+// grid (blocks of the larger segment, nseg), 256 threads; a block beyond its segment's pieces returns at once
+__global__ void k_tree_compact(CompactArgs g);
+
 }  // namespace mk

@@ -242,6 +242,9 @@ void tree_free(TreeHandle* t);
 int tree_assign(TreeHandle* t, const uint8_t* values, uint64_t n);
 int tree_update(TreeHandle* t, const uint64_t* idx, const uint8_t* values, uint64_t k);
 int tree_append(TreeHandle* t, const uint8_t* values, uint64_t k);
+// shrink: the first n values stay / the values at idx (any order, repeats count once) leave
+int tree_truncate(TreeHandle* t, uint64_t n);
+int tree_erase(TreeHandle* t, const uint64_t* idx, uint64_t k);
 int tree_root(TreeHandle* t, uint8_t* root);
 int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out);
 // each kind's TreeKind and an empty handle of its type for tree_new (null: the allocation failed)
@@ -258,6 +261,19 @@ TreeHandle* bytes_tree_handle();
 // lock with the device bound; t->count is the caller's to set.
 int tree_write_through_build(TreeHandle* t, uint64_t n_old, uint64_t n_new, uint64_t new_cap, const uint64_t* d_idx,
                              uint64_t k_idx, const void* d_values, hipStream_t st);
+
+// ---- shrinking a resident tree (list_tree_api.cpp) ------------------------------
+// What each kind's erase entry point and the handles run.  k_rm strictly
+// ascending removed indices (device) leave n_new = n_old - k_rm values, those
+// below `first` where they were; k_rm == 0: the first n_new <= n_old values
+// stay (a truncate).  moved = n_new - first values (0 for a truncate) and
+// their level-0 entries go through the workspace.
+uint64_t tree_shrink_ws(const TreeKind& K, uint64_t moved, uint32_t item_len);  // 0: item_len == 0 or moved >= 2^31
+int tree_shrink_check(const TreeKind& K, uint64_t n_old, uint64_t n_new, uint64_t capacity, uint32_t item_len,
+                      uint64_t k_rm, uint64_t first, uint64_t ws_bytes);  // no device needed
+int tree_shrink(const TreeKind& K, void* d_items, uint32_t item_len, void* d_level0, void* d_levels, uint64_t n_old,
+                uint64_t n_new, uint64_t capacity, const uint64_t* d_rm, uint64_t k_rm, uint64_t first,
+                void* d_root32, void* d_ws, hipStream_t st);
 
 // ---- several trees in one call (tree_many_api.cpp) ------------------------------------------
 // mk_ssz_trees_update_workspace_bytes with its error, and mk_dev_ssz_trees_update

@@ -258,6 +258,30 @@ int mk_dev_ssz_struct_list_tree_update(mk_call* call, void* d_records, uint64_t 
     return S.done(rc);
 }
 
+uint64_t mk_ssz_struct_list_tree_erase_workspace_bytes(uint64_t moved, uint32_t record_len) {
+    return tree_shrink_ws(kStructKind, moved, record_len);
+}
+
+// The records and their struct roots move; no record is hashed.  Every
+// argument check comes before the stream's device is looked up.
+int mk_dev_ssz_struct_list_tree_erase(mk_call* call, void* d_records, uint64_t n_old, uint64_t n_new,
+                                      uint64_t capacity, uint32_t record_len, const mk_field* fields,
+                                      uint32_t nfields, void* d_roots, void* d_levels, const uint64_t* d_rm,
+                                      uint64_t k_rm, uint64_t first, void* d_root32, void* d_ws, uint64_t ws_bytes,
+                                      void* stream) {
+    Scope S(call);
+    Layout L;
+    int rc = struct_tree_layout(fields, nfields, record_len, L);
+    if (!rc) rc = tree_shrink_check(kStructKind, n_old, n_new, capacity, record_len, k_rm, first, ws_bytes);
+    if (!rc) rc = struct_tree_check_ptrs(d_records, n_old, capacity, d_roots, d_levels, d_root32, d_ws);
+    if (!rc && k_rm && (!d_rm || ((uintptr_t)d_rm % 8))) rc = fail(MK_EINVAL, "null or misaligned index array");
+    if (!rc) rc = bind_stream((hipStream_t)stream);
+    if (!rc)
+        rc = tree_shrink(kStructKind, d_records, record_len, d_roots, d_levels, n_old, n_new, capacity, d_rm, k_rm,
+                         first, d_root32, d_ws, (hipStream_t)stream);
+    return S.done(rc);
+}
+
 int mk_struct_list_tree_new(mk_call* call, uint32_t record_len, const mk_field* fields, uint32_t nfields,
                             uint64_t capacity, mk_struct_list_tree** out) {
     Scope S(call);
@@ -293,6 +317,16 @@ int mk_struct_list_tree_update(mk_call* call, mk_struct_list_tree* t, const uint
 int mk_struct_list_tree_append(mk_call* call, mk_struct_list_tree* t, const uint8_t* records, uint64_t k) {
     Scope S(call);
     return S.done(tree_append(t, records, k));
+}
+
+int mk_struct_list_tree_truncate(mk_call* call, mk_struct_list_tree* t, uint64_t n) {
+    Scope S(call);
+    return S.done(tree_truncate(t, n));
+}
+
+int mk_struct_list_tree_erase(mk_call* call, mk_struct_list_tree* t, const uint64_t* idx, uint64_t k) {
+    Scope S(call);
+    return S.done(tree_erase(t, idx, k));
 }
 
 int mk_struct_list_tree_root(mk_call* call, mk_struct_list_tree* t, uint8_t root[32]) {

@@ -176,6 +176,54 @@ int tree_write_through_build(TreeHandle* t, uint64_t n_old, uint64_t n_new, uint
     return rebuild(t, n_new, st);
 }
 
+namespace {
+// the shrink on the handle's own buffers (under its lock); rm: k_rm sorted indices (host), uploaded into t->idx
+int shrink(TreeHandle* t, uint64_t n_new, const uint64_t* rm, uint64_t k_rm, uint64_t first, hipStream_t st) {
+    const uint32_t L = t->item_len;
+    const uint64_t need = tree_shrink_ws(*t->kind, k_rm ? n_new - first : 0, L);
+    TRY(grow(t->ws, need));
+    TRY(tree_shrink_check(*t->kind, t->count, n_new, t->cap, L, k_rm, first, t->ws.cap));
+    if (k_rm) {
+        TRY(grow(t->idx, 8 * k_rm));
+        HIPCHK(hipMemcpyAsync(t->idx.p, rm, 8 * k_rm, hipMemcpyHostToDevice, st));
+    }
+    TRY(tree_shrink(*t->kind, t->items.p, L, t->level0.p, t->levels.p, t->count, n_new, t->cap,
+                    (const uint64_t*)t->idx.p, k_rm, first, t->root.p, t->ws.p, st));
+    HIPCHK(hipStreamSynchronize(st));  // rm is released after this
+    t->count = n_new;
+    return MK_OK;
+}
+}  // namespace
+
+int tree_truncate(TreeHandle* t, uint64_t n) {
+    if (!t) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    if (n > t->count)
+        return fail(MK_EINVAL, "truncate to %llu of %llu %s", (unsigned long long)n, (unsigned long long)t->count,
+                    t->kind->noun);
+    if (n == t->count) return MK_OK;
+    TRY(bind_dev(t->dev));
+    return shrink(t, n, nullptr, 0, n, ctx()->stream);
+}
+
+int tree_erase(TreeHandle* t, const uint64_t* idx, uint64_t k) {
+    if (!t || (k && !idx)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    for (uint64_t i = 0; i < k; ++i)
+        if (idx[i] >= t->count)
+            return fail(MK_EINVAL, "index %llu beyond %llu %s", (unsigned long long)idx[i],
+                        (unsigned long long)t->count, t->kind->noun);
+    if (k == 0) return MK_OK;
+    std::vector<uint64_t> rm(idx, idx + k);
+    std::sort(rm.begin(), rm.end());
+    rm.erase(std::unique(rm.begin(), rm.end()), rm.end());
+    const uint64_t m = rm.size(), n_new = t->count - m;
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    if (rm[0] + m == t->count) return shrink(t, n_new, nullptr, 0, n_new, st);  // a suffix: nothing moves
+    return shrink(t, n_new, rm.data(), m, rm[0], st);
+}
+
 int tree_root(TreeHandle* t, uint8_t* root) {
     if (!t || !root) return fail(MK_EINVAL, "null pointer");
     std::lock_guard<std::mutex> tl(t->mu);

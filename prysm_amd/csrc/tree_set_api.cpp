@@ -243,6 +243,38 @@ int set_append(mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t k)
     return MK_OK;
 }
 
+// A shrink is not logged: everything pending is flushed (the
+// ordinary flush), then the tree shrinks at once; it enters the next flush
+// with nothing dirty, and the update over all the trees stores its new root
+// into the message as it does for every tree.  erase: the k values at idx leave; else: truncate to n.
+// A failed shrink leaves the set as the flush left it.
+int set_shrink(mk_tree_set* s, uint32_t tree, bool erase, const uint64_t* idx, uint64_t k, uint64_t n) {
+    if (!s || (erase && k && !idx)) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    TreeHandle* h = s->trees[tree].h;
+    sp::Pending& p = s->pend[tree];
+    const uint64_t count = p.count();
+    if (!erase && n > count)
+        return fail(MK_EINVAL, "truncate to %llu of %llu %s", (unsigned long long)n, (unsigned long long)count,
+                    h->kind->noun);
+    for (uint64_t i = 0; erase && i < k; ++i)
+        if (idx[i] >= count)
+            return fail(MK_EINVAL, "index %llu beyond %llu %s", (unsigned long long)idx[i], (unsigned long long)count,
+                        h->kind->noun);
+    if (erase ? k == 0 : n == count) return MK_OK;
+    if (s->dirty) {
+        TRY(bind_set(s));
+        TRY(flush(s));
+        HIPCHK(hipStreamSynchronize(ctx()->stream));
+        flushed(s);
+    }
+    TRY(erase ? tree_erase(h, idx, k) : tree_truncate(h, n));
+    sp::record_assign(p, h->count, h->cap);
+    s->dirty = true;  // its root in the message is the old one
+    return MK_OK;
+}
+
 int set_root(mk_tree_set* s, uint8_t* root) {
     if (!s || !root) return fail(MK_EINVAL, "null pointer");
     std::lock_guard<std::mutex> lk(s->mu);
@@ -335,6 +367,16 @@ int mk_tree_set_update(mk_call* call, mk_tree_set* s, uint32_t tree, const uint6
 int mk_tree_set_append(mk_call* call, mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t k) {
     Scope S(call, false);
     return S.done(set_append(s, tree, values, k));
+}
+
+int mk_tree_set_truncate(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t n) {
+    Scope S(call);
+    return S.done(set_shrink(s, tree, false, nullptr, 0, n));
+}
+
+int mk_tree_set_erase(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k) {
+    Scope S(call);
+    return S.done(set_shrink(s, tree, true, idx, k, 0));
 }
 
 uint64_t mk_tree_set_count(const mk_tree_set* s, uint32_t tree) {

@@ -710,6 +710,43 @@ def bytes_list_tree_update(elems: torch.Tensor, n_old: int, n_new: int, capacity
     return root
 
 
+def tree_erase_workspace_bytes(kind: int, moved: int, item_len: int) -> int:
+    """Workspace of ``tree_erase`` of a tree of ``kind`` (``_lib.MK_TREE_*``):
+    moved = n_new - first values of an erase, 0 for a truncate."""
+    name = {_lib.MK_TREE_LIST: "list", _lib.MK_TREE_STRUCT: "struct_list", _lib.MK_TREE_BYTES: "bytes_list"}[kind]
+    return getattr(_lib.load(), f"mk_ssz_{name}_tree_erase_workspace_bytes")(moved, item_len)
+
+
+def tree_erase(kind: int, items: torch.Tensor, n_old: int, n_new: int, capacity: int, item_len: int,
+               levels: torch.Tensor, root: torch.Tensor, rm: torch.Tensor = None, k_rm: int = 0, first: int = 0,
+               level0: torch.Tensor = None, spec=None, ws: torch.Tensor = None) -> torch.Tensor:
+    """Shrink a built tree of ``kind`` on the device (``mk_dev_ssz_*_tree_erase``,
+    DESIGN.md §5k): the values at the ``k_rm`` strictly ascending 64-bit device
+    indices ``rm`` (all >= ``first``) leave and the survivors close the gaps in
+    order (n_new == n_old - k_rm); ``k_rm == 0``: the first n_new <= n_old
+    values stay.  ``level0``: the struct roots / element digests, which move
+    with their values; ``spec``: a struct tree's field layout.  Returns ``root``."""
+    from .registry import _fields
+
+    dev = _dev(items)
+    if k_rm and (rm is None or rm.numel() < k_rm or rm.element_size() != 8):
+        raise ValueError("rm: k_rm 64-bit device indices")
+    if (kind != _lib.MK_TREE_LIST) != (level0 is not None):
+        raise ValueError("level0 goes with a struct or bytes tree")
+    if ws is None:
+        ws = torch.empty(tree_erase_workspace_bytes(kind, n_new - first if k_rm else 0, item_len), dtype=torch.uint8,
+                         device=items.device)
+    tail = (_p(levels), _p(rm) if k_rm else None, k_rm, first, _p(root), _p(ws), ws.numel(), _stream(items.device))
+    head = (_p(items), n_old, n_new, capacity, item_len)
+    if kind == _lib.MK_TREE_LIST:
+        _lib.invoke("mk_dev_ssz_list_tree_erase", *head, *tail, device=dev)
+    elif kind == _lib.MK_TREE_STRUCT:
+        _lib.invoke("mk_dev_ssz_struct_list_tree_erase", *head, _fields(spec), len(spec), _p(level0), *tail, device=dev)
+    else:
+        _lib.invoke("mk_dev_ssz_bytes_list_tree_erase", *head, _p(level0), *tail, device=dev)
+    return root
+
+
 class TreeArgs:
     """One tree of ``trees_update`` (mk_tree_update): the arguments of that
     kind's own ``*_tree_update`` wrapper.  ``kind`` is _lib.MK_TREE_LIST /

@@ -106,6 +106,19 @@ class _Tree:
         a = self._flat(values)
         self._call("append", _ptr(a), a.size // self._len)
 
+    def truncate(self, n: int) -> None:
+        """Keep the first ``n`` values (on the device: nothing is uploaded);
+        ``n`` > len(self) raises and changes nothing."""
+        self._call("truncate", int(n))
+
+    def erase(self, indices) -> None:
+        """Remove the values at ``indices`` (any order, a repeat counts once)
+        and close the gaps in order, on the device: only the indices are
+        uploaded, and no survivor is hashed again.  An index >= len(self)
+        raises and changes nothing."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        self._call("erase", _ptr(idx), idx.size)
+
     def root(self) -> bytes:
         """merkleHash (ListTree) / TreeHash (the other two) of the current list."""
         out = ctypes.create_string_buffer(32)
@@ -256,6 +269,21 @@ class TreeSet:
         tree = self._tree(tree)
         a = self._flat(tree, values)
         self._call("append", tree, _ptr(a), a.size // self._len[tree])
+
+    def truncate(self, tree, n: int) -> None:
+        """Keep the first ``n`` values of a tree.  Not recorded: whatever the
+        set has pending is flushed, then the tree shrinks on the device at
+        once (``BeaconTreeSet``: ``truncate("eth1_votes", 0)`` at the end of a
+        voting period)."""
+        self._call("truncate", self._tree(tree), int(n))
+
+    def erase(self, tree, indices) -> None:
+        """Remove the values at ``indices`` (any order, a repeat counts once)
+        of a tree and close the gaps in order, at once as ``truncate``
+        (``BeaconTreeSet``: ``erase("attestations", dropped)`` is
+        CleanupAttestations)."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        self._call("erase", self._tree(tree), _ptr(idx), idx.size)
 
     def count(self, tree) -> int:
         """Items of a tree, pending appends included."""
