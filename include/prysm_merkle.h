@@ -227,6 +227,55 @@ int mk_list_tree_erase(mk_call* call, mk_list_tree* t, const uint64_t* idx, uint
 int mk_list_tree_root(mk_call* call, mk_list_tree* t, uint8_t root[32]);
 /* Items [first, first + cnt), cnt x item_len bytes. */
 int mk_list_tree_items(mk_call* call, mk_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
+/* Merkle proofs out of a resident tree and their batched verifier (DESIGN.md
+ * §5l).  For n items of s = item_len bytes, 1 <= s <= 128: p = 128 / s items
+ * per chunk, cb = p * s, nchunks = ceil(n / p), total = n * s, D the smallest
+ * d with ceil(nchunks / 2^d) == 1.  The record of item i < n is
+ * 256 + 32 * max(D - 1, 0) bytes (mk_ssz_list_branch_bytes; 0 for item_len 0
+ * or above 128): window[256] = the list bytes [2 j cb, min(total, (2 j + 2)
+ * cb)) with j = (i / p) / 2 ([0, total) for nchunks <= 1), zeros after them;
+ * then sib[d], d = 1 .. D - 1: the stored level-d node (j >> (d - 1)) ^ 1, or
+ * 0^32 when that index is >= ceil(nchunks / 2^d).  The level-1 sibling is in
+ * the window.  The record of an index >= n is all zeros (device indices are
+ * not checked on the host).
+ * mk_dev_ssz_list_tree_branches gathers k records (k x stride bytes, 16-B
+ * aligned) from d_level0 -- the item buffer of a list tree, or d_roots /
+ * d_digests of a struct / bytes tree with item_len = 32 -- and the level array
+ * of mk_ssz_list_tree_levels_bytes(capacity, item_len).  No node at or beyond
+ * a level's current count and no item byte at or beyond total is read.  One
+ * launch: allocates nothing, never synchronises, capturable into a hipGraph.
+ * Verify (value, i, n, s, record, root), false for i >= n: the window with
+ * the value written over the item's bytes; for nchunks <= 1 top = its first
+ * total bytes, else node = K(window[0, wl)) (0^128 appended when 2 j + 1 ==
+ * nchunks) folded for d = 1 .. D - 1 with q = j >> (d - 1): K(sib[d] || node)
+ * for odd q, K(node || sib[d]) when q + 1 < ceil(nchunks / 2^d), else
+ * K(node || 0^128) (the slot is ignored); list_root = K(top || le64(n) ||
+ * 0^24).  With d_container (container_len <= MK_CONTAINER_MAX, container_off
+ * + 32 <= container_len) the compared value is K(container with list_root at
+ * container_off), else list_root; against d_roots[0] (root_stride 0) or
+ * d_roots[32 g] (root_stride 32).  d_ok: one byte per proof.
+ * Every argument check comes before a device is looked up: null or
+ * misaligned pointers, item_len 0 or above 128, n > capacity, k >= 2^31, a
+ * root_stride other than 0 or 32 and a bad container_off are MK_EINVAL. */
+uint64_t mk_ssz_list_branch_bytes(uint64_t n, uint32_t item_len);
+int mk_dev_ssz_list_tree_branches(mk_call* call, const void* d_level0, uint64_t n, uint64_t capacity,
+                                  uint32_t item_len, const void* d_levels, const uint64_t* d_idx, uint64_t k,
+                                  void* d_branches, void* stream);
+int mk_dev_verify_list_branches(mk_call* call, const void* d_values, const uint64_t* d_idx, uint64_t k, uint64_t n,
+                                uint32_t item_len, const void* d_branches, const void* d_roots, uint32_t root_stride,
+                                const void* d_container, uint32_t container_len, uint32_t container_off, void* d_ok,
+                                void* stream);
+int mk_verify_list_branches(mk_call* call, const uint8_t* values, const uint64_t* idx, uint64_t k, uint64_t n,
+                            uint32_t item_len, const uint8_t* branches, const uint8_t* roots, uint32_t root_stride,
+                            const uint8_t* container, uint32_t container_len, uint32_t container_off, uint8_t* ok);
+/* Handle form: the proofs of the items at k host indices (any order, repeats
+ * allowed; an index >= count is MK_EINVAL and nothing is written; k == 0 a
+ * no-op).  values_out gets the k level-0 values (k x item_len bytes; 32-B
+ * struct roots / element digests for the other two kinds), branches_out the k
+ * records of mk_ssz_list_branch_bytes(count, item_len or 32) bytes.  One upload
+ * of the indices, one launch, one read-back.  item_len above 128 is MK_EINVAL. */
+int mk_list_tree_branches(mk_call* call, mk_list_tree* t, const uint64_t* idx, uint64_t k, uint8_t* values_out,
+                          uint8_t* branches_out);
 
 /* ---- subtree sharding across GPUs ----------------------- */
 /* Split a merkleHash of n items over `nshards` devices: every shard is a
@@ -541,6 +590,9 @@ int mk_struct_list_tree_erase(mk_call* call, mk_struct_list_tree* t, const uint6
 int mk_struct_list_tree_root(mk_call* call, mk_struct_list_tree* t, uint8_t root[32]);
 /* Records [first, first + cnt), cnt x record_len bytes. */
 int mk_struct_list_tree_records(mk_call* call, mk_struct_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
+/* mk_list_tree_branches over the 32-B struct roots: values_out gets k x 32 bytes (the proven leaves). */
+int mk_struct_list_tree_branches(mk_call* call, mk_struct_list_tree* t, const uint64_t* idx, uint64_t k,
+                                 uint8_t* values_out, uint8_t* branches_out);
 
 /* ---- device-resident bytes tree: a [][N]byte list re-hashed from changed elements --- */
 /* TreeHash of a list of n byte strings of elem_len bytes each (1 .. 2^30; the
@@ -621,6 +673,9 @@ int mk_bytes_list_tree_erase(mk_call* call, mk_bytes_list_tree* t, const uint64_
 int mk_bytes_list_tree_root(mk_call* call, mk_bytes_list_tree* t, uint8_t root[32]);
 /* Elements [first, first + cnt), cnt x elem_len bytes. */
 int mk_bytes_list_tree_elems(mk_call* call, mk_bytes_list_tree* t, uint64_t first, uint64_t cnt, uint8_t* out);
+/* mk_list_tree_branches over the 32-B element digests K(le32(N) || e_i): values_out gets k x 32 bytes. */
+int mk_bytes_list_tree_branches(mk_call* call, mk_bytes_list_tree* t, const uint64_t* idx, uint64_t k,
+                                uint8_t* values_out, uint8_t* branches_out);
 
 /* ---- several device-resident trees, and the struct that holds them, in one call --- */
 /* mk_dev_ssz_trees_update runs the update of up to MK_TREES_MAX resident trees
@@ -754,6 +809,14 @@ uint64_t mk_tree_set_count(const mk_tree_set* s, uint32_t tree);
 int mk_tree_set_root(mk_call* call, mk_tree_set* s, uint8_t root[32]);
 int mk_tree_set_tree_root(mk_call* call, mk_tree_set* s, uint32_t tree, uint8_t root[32]);
 int mk_tree_set_items(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t first, uint64_t cnt, uint8_t* out);
+/* Proofs out of one tree of the set (mk_list_tree_branches against
+ * count(tree), pending appends included): flushes whatever is pending, as a
+ * root does, then runs the tree's launch.  container_out (may be NULL;
+ * container_len bytes, nothing for a set without a container) gets the hash
+ * message with every tree's root in place: mk_verify_list_branches takes it
+ * with the tree's container offset and compares with mk_tree_set_root. */
+int mk_tree_set_branches(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k,
+                         uint8_t* values_out, uint8_t* branches_out, uint8_t* container_out);
 
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves

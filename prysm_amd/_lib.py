@@ -187,6 +187,15 @@ _SIGS = {
     "mk_tree_set_root": (_int, [_cp, _vp, _vp]),
     "mk_tree_set_tree_root": (_int, [_cp, _vp, _u32, _vp]),
     "mk_tree_set_items": (_int, [_cp, _vp, _u32, _u64, _u64, _vp]),
+    "mk_ssz_list_branch_bytes": (_u64, [_u64, _u32]),
+    "mk_dev_ssz_list_tree_branches": (_int, [_cp, _vp, _u64, _u64, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "mk_dev_verify_list_branches": (_int, [_cp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp,
+                                           _vp]),
+    "mk_verify_list_branches": (_int, [_cp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp]),
+    "mk_list_tree_branches": (_int, [_cp, _vp, _vp, _u64, _vp, _vp]),
+    "mk_struct_list_tree_branches": (_int, [_cp, _vp, _vp, _u64, _vp, _vp]),
+    "mk_bytes_list_tree_branches": (_int, [_cp, _vp, _vp, _u64, _vp, _vp]),
+    "mk_tree_set_branches": (_int, [_cp, _vp, _u32, _vp, _u64, _vp, _vp, _vp]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),

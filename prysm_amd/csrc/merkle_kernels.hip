@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "keccak_dev.hpp"
+#include "list_branch.hpp"
 #include "merkle_kernels.hpp"
 #include "tree_compact.hpp"
 
@@ -4801,6 +4802,193 @@ __global__ __launch_bounds__(256) void k_tree_compact(CompactArgs g) {
         *reinterpret_cast<uint32_t*>(dst) = *reinterpret_cast<const uint32_t*>(src);
     else
         *dst = *src;
+}
+
+// ----------------------------------------------------------------------------
+// Merkle proofs out of a resident list tree: a gather.  Each
+// wave writes one record per turn (grid stride over the indices) as one
+// contiguous run of 16-B pieces: piece q < 16 is bytes [16 q, 16 q + 16) of
+// the item's 256-B window -- one 16-B load where the window's base is 16-B
+// aligned and the piece lies inside the list, byte loads below `total`
+// otherwise (an item length such as 100 puts windows at 200 j), zero without a
+// load past the window's end -- and lane pair (16 + 2 (d - 1), + 1) takes the
+// two halves of sib[d], the stored level-d node (j >> (d - 1)) ^ 1, read only
+// when it is below the level's count of the CURRENT list (list_branch.hpp):
+// what a shrink left to the right of the new end is never loaded.  An index
+// >= n gives a zero record.  No hand-off between waves, no counter, no
+// workspace; the level offsets are per-workgroup LDS.
+__global__ __launch_bounds__(64 * kBranchWaves) void k_list_tree_branches(
+    const uint8_t* __restrict__ level0, const uint4* __restrict__ levels, uint64_t n, uint64_t capacity,
+    uint32_t item_len, const uint64_t* __restrict__ indices, uint64_t k, uint4* __restrict__ out) {
+    __shared__ uint64_t lvoff[64];  // first node of level d in the level array
+    const BranchShape b = branch_shape(n, capacity, item_len);
+    const uint32_t w = threadIdx.x >> 6, L = threadIdx.x & 63u;
+    if (w == 0) lvoff[L] = (L >= 1 && L < b.D) ? branch_level_off(b, L) : 0;
+    __syncthreads();
+    const uint32_t pieces = (uint32_t)(branch_record_bytes(b) / 16);
+    const uint64_t stride = (uint64_t)gridDim.x * kBranchWaves;
+    for (uint64_t g = (uint64_t)blockIdx.x * kBranchWaves + w; g < k; g += stride) {
+        const uint64_t i = indices[g];
+        const bool live = i < n;  // wave-uniform
+        uint64_t j = 0, lo = 0;
+        uint32_t wl = 0;
+        if (live) {
+            j = branch_window_index(b, i);
+            branch_window(b, j, &lo, &wl);
+        }
+        const uint8_t* wsrc = level0 + lo;
+        const bool aligned = (((uintptr_t)wsrc) & 15u) == 0;
+        for (uint32_t q = L; q < pieces; q += 64) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (live && q < 16u) {
+                const uint32_t a = 16u * q;
+                if (aligned && a + 16u <= wl) {
+                    v = *reinterpret_cast<const uint4*>(wsrc + a);
+                } else if (a < wl) {
+                    uint32_t t[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (uint32_t e = 0; e < 16u; ++e)
+                        if (a + e < wl) t[e >> 2] |= (uint32_t)wsrc[a + e] << (8u * (e & 3u));
+                    v = make_uint4(t[0], t[1], t[2], t[3]);
+                }
+            } else if (live) {
+                const uint32_t d = 1u + ((q - 16u) >> 1), h = (q - 16u) & 1u;
+                uint64_t node;
+                if (branch_sibling(b, j, d, &node)) v = levels[2 * (lvoff[d] + node) + h];
+            }
+            out[(uint64_t)pieces * g + q] = v;
+        }
+    }
+}
+
+// The byte sponge of sponge_generic over a message whose bytes [sub_lo, sub_lo
+// + sub_len) come from `sub` instead of p: message = A' || 0^lz || (lenc ?
+// le64(nval) || 0^24 : -), A'[m] = sub(m - sub_lo) inside the range, p[m]
+// elsewhere (m < la).  The source switches per byte, so no thread keeps a copy
+// of the message.
+template <class Sub>
+__device__ __forceinline__ void sponge_subst(const uint8_t* __restrict__ p, uint32_t la, uint32_t sub_lo,
+                                             uint32_t sub_len, const Sub& sub, uint32_t lz, bool lenc, uint64_t nval,
+                                             uint4& d0, uint4& d1) {
+    const uint32_t len = la + lz + (lenc ? 32u : 0u);
+    const uint32_t nb = len / 136 + 1;
+    const bool aligned = (((uintptr_t)p) & 7u) == 0;
+    State s;
+    zero(s);
+    for (uint32_t blk = 0; blk < nb; ++blk) {
+        const uint32_t base = blk * 136;
+#pragma unroll
+        for (int w = 0; w < 17; ++w) {
+            const uint32_t m0 = base + 8u * w;
+            uint32_t lo = 0, hi = 0;
+            if (aligned && m0 + 8 <= la && (m0 + 8 <= sub_lo || m0 >= sub_lo + sub_len)) {
+                const uint2 v = *reinterpret_cast<const uint2*>(p + m0);
+                lo = v.x;
+                hi = v.y;
+            } else if (m0 < len) {
+#pragma unroll 1
+                for (int q = 0; q < 8; ++q) {
+                    const uint32_t m = m0 + q;
+                    uint32_t byte = 0;
+                    if (m < la) {
+                        byte = (m - sub_lo < sub_len) ? sub(m - sub_lo) : (uint32_t)p[m];
+                    } else if (m >= la + lz && m < len) {
+                        const uint32_t e = m - la - lz;  // lenc byte
+                        byte = e < 8 ? (uint32_t)((nval >> (8 * e)) & 0xFF) : 0u;
+                    }
+                    if (q < 4)
+                        lo |= byte << (8 * q);
+                    else
+                        hi |= byte << (8 * (q - 4));
+                }
+            }
+            if (m0 <= len && len < m0 + 8) {  // domain pad byte 0x01
+                const uint32_t q = len - m0;
+                if (q < 4)
+                    lo ^= 1u << (8 * q);
+                else
+                    hi ^= 1u << (8 * (q - 4));
+            }
+            if (blk == nb - 1 && w == 16) hi ^= 0x80000000u;
+            s.lo[w] ^= lo;
+            s.hi[w] ^= hi;
+        }
+        keccak_f(s);
+    }
+    digest(s, d0, d1);
+}
+
+// Batched verification of list-tree proofs, one proof per
+// thread: the window with the caller's value written over the item's bytes
+// through the byte sponge (at most 384 B: the window, 0^128 when its second
+// chunk does not exist), the fold over sib[1 .. D - 1] (64-B messages, 160-B
+// ones where the sibling does not exist: its slot is not read), the mix-in of
+// n, and with a container the hash of its message with the list root in place
+// of bytes [container_off, +32).  Compared with the batch's one root
+// (root_stride == 0) or root g (32).  A dependent chain of D + 2 .. D + 6
+// permutations per thread and a handful of loads: latency-bound, as
+// k_verify_deposits.
+__global__ __launch_bounds__(256) void k_verify_list_branches(
+    const uint8_t* __restrict__ values, const uint64_t* __restrict__ indices, uint64_t k, uint64_t n,
+    uint32_t item_len, const uint8_t* __restrict__ branches, const uint8_t* __restrict__ roots, uint32_t root_stride,
+    const uint8_t* __restrict__ container, uint32_t container_len, uint32_t container_off,
+    uint8_t* __restrict__ ok) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    const uint64_t i = indices[g];
+    if (i >= n) {
+        ok[g] = 0;
+        return;
+    }
+    const BranchShape b = branch_shape(n, n, item_len);  // the capacity only places the levels
+    const uint8_t* rec = branches + branch_record_bytes(b) * g;
+    const uint8_t* val = values + (uint64_t)item_len * g;
+    const uint64_t j = branch_window_index(b, i);
+    const uint32_t pos = branch_item_pos(b, i);
+    uint64_t lo;
+    uint32_t wl;
+    branch_window(b, j, &lo, &wl);
+    const auto value_byte = [&](uint32_t e) { return (uint32_t)val[e]; };
+    uint4 v0, v1;
+    if (b.nchunks < 2) {  // the top is the raw chunk
+        sponge_subst(rec, wl, pos, item_len, value_byte, 0u, true, n, v0, v1);
+    } else {
+        sponge_subst(rec, wl, pos, item_len, value_byte, branch_window_padded(b, j) ? 128u : 0u, false, 0, v0, v1);
+        const uint4* sib = reinterpret_cast<const uint4*>(rec + kBranchWindow);
+        for (uint32_t d = 1; d < b.D; ++d) {
+            const uint64_t q = j >> (d - 1);
+            const bool right = (q & 1u) != 0, pad = !right && q + 1 >= branch_level_count(b, d);
+            uint4 s0 = make_uint4(0, 0, 0, 0), s1 = s0;
+            if (!pad) {
+                s0 = sib[2 * (d - 1)];
+                s1 = sib[2 * (d - 1) + 1];
+            }
+            if (right)
+                hash_pair(s0, s1, v0, v1, false, v0, v1);
+            else
+                hash_pair(v0, v1, s0, s1, pad, v0, v1);
+        }
+        hash_final(v0, v1, n, v0, v1);
+    }
+    if (container) {
+        const uint4 r0 = v0, r1 = v1;
+        const auto root_byte = [&](uint32_t e) {
+            const uint32_t wd = e >> 2;
+            const uint32_t x = wd == 0   ? r0.x
+                               : wd == 1 ? r0.y
+                               : wd == 2 ? r0.z
+                               : wd == 3 ? r0.w
+                               : wd == 4 ? r1.x
+                               : wd == 5 ? r1.y
+                               : wd == 6 ? r1.z
+                                         : r1.w;
+            return (x >> (8u * (e & 3u))) & 0xFFu;
+        };
+        sponge_subst(container, container_len, container_off, 32u, root_byte, 0u, false, 0, v0, v1);
+    }
+    const uint32_t* rt = reinterpret_cast<const uint32_t*>(roots + (root_stride ? 32 * g : 0));
+    ok[g] = (v0.x == rt[0] && v0.y == rt[1] && v0.z == rt[2] && v0.w == rt[3] && v1.x == rt[4] && v1.y == rt[5] &&
+             v1.z == rt[6] && v1.w == rt[7]);
 }
 
 }  // namespace mk

@@ -254,4 +254,14 @@ struct CompactArgs {
 // grid (blocks of the larger segment, nseg), 256 threads; a block beyond its segment's pieces returns at once
 __global__ void k_tree_compact(CompactArgs g);
 
+// Merkle proofs of a resident list tree (tree_branch_api.cpp; the arithmetic: list_branch.hpp).
+// One record per wave and turn, kBranchWaves waves per workgroup: the item's 256-B window, then sib[1 .. D - 1].
+__global__ void k_list_tree_branches(const uint8_t* level0, const uint4* levels, uint64_t n, uint64_t capacity,
+                                     uint32_t item_len, const uint64_t* indices, uint64_t k, uint4* out);
+// one proof per thread: the window with the caller's value in place, the fold, the mix-in, the container
+__global__ void k_verify_list_branches(const uint8_t* values, const uint64_t* indices, uint64_t k, uint64_t n,
+                                       uint32_t item_len, const uint8_t* branches, const uint8_t* roots,
+                                       uint32_t root_stride, const uint8_t* container, uint32_t container_len,
+                                       uint32_t container_off, uint8_t* ok);
+
 }  // namespace mk

@@ -247,6 +247,9 @@ int tree_truncate(TreeHandle* t, uint64_t n);
 int tree_erase(TreeHandle* t, const uint64_t* idx, uint64_t k);
 int tree_root(TreeHandle* t, uint8_t* root);
 int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out);
+// Merkle proofs of the k values at idx (any order, repeats allowed): the k level-0 values
+// (items, struct roots, element digests) and the k records; one upload, one launch, one read-back
+int tree_branches(TreeHandle* t, const uint64_t* idx, uint64_t k, uint8_t* values_out, uint8_t* branches_out);
 // each kind's TreeKind and an empty handle of its type for tree_new (null: the allocation failed)
 const TreeKind& list_tree_kind();
 const TreeKind& struct_tree_kind();
@@ -274,6 +277,13 @@ int tree_shrink_check(const TreeKind& K, uint64_t n_old, uint64_t n_new, uint64_
 int tree_shrink(const TreeKind& K, void* d_items, uint32_t item_len, void* d_level0, void* d_levels, uint64_t n_old,
                 uint64_t n_new, uint64_t capacity, const uint64_t* d_rm, uint64_t k_rm, uint64_t first,
                 void* d_root32, void* d_ws, hipStream_t st);
+
+// ---- Merkle proofs of a resident tree (tree_branch_api.cpp) --------------------
+// mk_dev_ssz_list_tree_branches: every argument check (no device needed), then the one launch on st
+int list_branches_check(const void* d_level0, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
+                        const uint64_t* d_idx, uint64_t k, const void* d_branches);
+int list_branches_launch(const void* d_level0, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
+                         const uint64_t* d_idx, uint64_t k, void* d_branches, hipStream_t st);
 
 // ---- several trees in one call (tree_many_api.cpp) ------------------------------------------
 // mk_ssz_trees_update_workspace_bytes with its error, and mk_dev_ssz_trees_update

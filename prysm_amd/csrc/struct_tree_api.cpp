@@ -339,4 +339,10 @@ int mk_struct_list_tree_records(mk_call* call, mk_struct_list_tree* t, uint64_t 
     return S.done(tree_read(t, first, cnt, out));
 }
 
+int mk_struct_list_tree_branches(mk_call* call, mk_struct_list_tree* t, const uint64_t* idx, uint64_t k,
+                                 uint8_t* values_out, uint8_t* branches_out) {
+    Scope S(call);
+    return S.done(tree_branches(t, idx, k, values_out, branches_out));
+}
+
 }  // extern "C"

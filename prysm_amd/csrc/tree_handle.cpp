@@ -3,6 +3,7 @@
 // list, its level 0 and its levels in HBM, assign / update / append / root /
 // read-back under one mutex.  What a kind does differently is its TreeKind
 // (runtime.hpp), defined in list_tree_api, struct_tree_api, bytes_tree_api.
+#include "list_branch.hpp"
 #include "runtime.hpp"
 
 using namespace mk;
@@ -245,6 +246,38 @@ int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out) {
     const uint32_t L = t->item_len;
     HIPCHK(hipMemcpyAsync(out, (const uint8_t*)t->items.p + first * L, cnt * L, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return MK_OK;
+}
+
+// The proofs of k values: the indices up, one gather launch
+// over level 0 and the levels, the records back.  A value lies in its
+// record's window, so the k level-0 values are copied out of the records on
+// the host: no second read-back.
+int tree_branches(TreeHandle* t, const uint64_t* idx, uint64_t k, uint8_t* values_out, uint8_t* branches_out) {
+    if (!t || (k && (!idx || !values_out || !branches_out))) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    for (uint64_t i = 0; i < k; ++i)
+        if (idx[i] >= t->count)
+            return fail(MK_EINVAL, "index %llu beyond %llu %s", (unsigned long long)idx[i],
+                        (unsigned long long)t->count, t->kind->noun);
+    if (k == 0) return MK_OK;
+    const uint32_t L = t->kind->level0 ? 32 : t->item_len;  // a leaf: the item, or its 32-B root / digest
+    const uint64_t stride = mk_ssz_list_branch_bytes(t->count, L);
+    if (!stride) return fail(MK_EINVAL, "item_len %u above %u: no proof record", L, kBranchItemMax);
+    if (k >= kMaxWork) return fail(MK_EINVAL, "%llu proofs in one call (limit 2^31 - 1)", (unsigned long long)k);
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    const void* leaves = t->kind->level0 ? t->level0.p : t->items.p;
+    TRY(grow(t->idx, 8 * k));
+    TRY(grow(t->ws, stride * k));
+    TRY(list_branches_check(leaves, t->count, t->cap, L, t->levels.p, (const uint64_t*)t->idx.p, k, t->ws.p));
+    HIPCHK(hipMemcpyAsync(t->idx.p, idx, 8 * k, hipMemcpyHostToDevice, st));
+    TRY(list_branches_launch(leaves, t->count, t->cap, L, t->levels.p, (const uint64_t*)t->idx.p, k, t->ws.p, st));
+    HIPCHK(hipMemcpyAsync(branches_out, t->ws.p, stride * k, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // idx is released after this
+    const BranchShape b = branch_shape(t->count, t->cap, L);
+    for (uint64_t g = 0; g < k; ++g)
+        std::memcpy(values_out + g * L, branches_out + g * stride + branch_item_pos(b, idx[g]), L);
     return MK_OK;
 }
 

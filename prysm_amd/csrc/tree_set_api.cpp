@@ -307,6 +307,43 @@ int set_items(mk_tree_set* s, uint32_t tree, uint64_t first, uint64_t cnt, uint8
     return tree_read(s->trees[tree].h, first, cnt, out);
 }
 
+// Proofs out of one tree of the set: everything pending is
+// flushed as for a root, then the tree's own launch and read-back, then the
+// message as the device holds it, every tree's root in place -- what a
+// verifier hashes with the proven list's root substituted.  No tree takes part
+// in the container: the message is what put() wrote.
+int set_branches(mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k, uint8_t* values_out,
+                 uint8_t* branches_out, uint8_t* container_out) {
+    if (!s || (k && (!idx || !values_out || !branches_out))) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    TreeHandle* h = s->trees[tree].h;
+    const uint64_t count = s->pend[tree].count();
+    for (uint64_t i = 0; i < k; ++i)
+        if (idx[i] >= count)
+            return fail(MK_EINVAL, "index %llu beyond %llu %s", (unsigned long long)idx[i], (unsigned long long)count,
+                        h->kind->noun);
+    if (k >= kMaxWork) return fail(MK_EINVAL, "%llu proofs in one call (limit 2^31 - 1)", (unsigned long long)k);
+    const bool want_msg = container_out && s->container_len;
+    if (k == 0 && !want_msg) return MK_OK;
+    TRY(bind_set(s));
+    if (s->dirty) {
+        TRY(flush(s));
+        HIPCHK(hipStreamSynchronize(ctx()->stream));
+        flushed(s);
+    }
+    TRY(tree_branches(h, idx, k, values_out, branches_out));
+    if (!want_msg) return MK_OK;
+    if (nparts(s) == 0) {
+        std::memcpy(container_out, s->msg.data(), s->container_len);
+        return MK_OK;
+    }
+    hipStream_t st = ctx()->stream;
+    HIPCHK(hipMemcpyAsync(container_out, s->stage.p, s->container_len, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -398,6 +435,12 @@ int mk_tree_set_tree_root(mk_call* call, mk_tree_set* s, uint32_t tree, uint8_t 
 int mk_tree_set_items(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t first, uint64_t cnt, uint8_t* out) {
     Scope S(call);
     return S.done(set_items(s, tree, first, cnt, out));
+}
+
+int mk_tree_set_branches(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k,
+                         uint8_t* values_out, uint8_t* branches_out, uint8_t* container_out) {
+    Scope S(call);
+    return S.done(set_branches(s, tree, idx, k, values_out, branches_out, container_out));
 }
 
 }  // extern "C"

@@ -584,6 +584,67 @@ def list_tree_update(items: torch.Tensor, n_old: int, n_new: int, capacity: int,
     return root
 
 
+def list_branch_bytes(n: int, item_len: int) -> int:
+    """Bytes of one proof record of a list of n item_len-byte items (0: item_len 0 or above 128)."""
+    return _lib.load().mk_ssz_list_branch_bytes(n, item_len)
+
+
+def list_tree_branches(level0: torch.Tensor, n: int, capacity: int, item_len: int, levels: torch.Tensor,
+                       indices: torch.Tensor, k: int = None, out: torch.Tensor = None) -> torch.Tensor:
+    """Merkle proofs of the items at the k device ``indices`` (int64 / uint64,
+    any order) of a built resident tree, one launch: (k * list_branch_bytes(n,
+    item_len),) uint8 (mk_dev_ssz_list_tree_branches).
+    ``level0``: the item buffer of a list tree, or the struct roots / element
+    digests of the other two kinds with item_len = 32.  An index >= n gives a
+    zero record.  Nothing is read on the host, so a captured call follows the
+    tensors' contents at replay."""
+    dev = _dev(level0)
+    if k is None:
+        k = indices.numel()
+    if indices.element_size() != 8 or indices.numel() < k:
+        raise ValueError("indices: at least k 64-bit integers")
+    if level0.numel() * level0.element_size() < n * item_len:
+        raise ValueError("level 0 shorter than n * item_len")
+    if levels.numel() * levels.element_size() < list_tree_levels_bytes(capacity, item_len):
+        raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, item_len)")
+    need = list_branch_bytes(n, item_len) * k
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=level0.device)
+    elif out.numel() * out.element_size() < need:
+        raise ValueError("branch buffer smaller than k records")
+    _lib.invoke("mk_dev_ssz_list_tree_branches", _p(level0), n, capacity, item_len, _p(levels), _p(indices), k,
+                _p(out), _stream(level0.device), device=dev)
+    return out
+
+
+def verify_list_branches(values: torch.Tensor, indices: torch.Tensor, k: int, n: int, item_len: int,
+                         branches: torch.Tensor, roots: torch.Tensor, root_stride: int = 0,
+                         container: torch.Tensor = None, container_off: int = 0,
+                         out: torch.Tensor = None) -> torch.Tensor:
+    """Verify k list-tree proofs resident on the device: (k,) uint8, 1 where
+    ``values[g]`` at index ``indices[g]`` of a list of n items folds through
+    record g to the root -- ``roots``' first 32 bytes (root_stride 0) or root
+    g (32).  With ``container`` (the struct's hash message) the list root is
+    substituted at ``container_off`` and the message's hash is compared
+    (mk_dev_verify_list_branches)."""
+    dev = _dev(branches)
+    if indices.element_size() != 8 or indices.numel() < k:
+        raise ValueError("indices: at least k 64-bit integers")
+    if values.numel() * values.element_size() < k * item_len:
+        raise ValueError("values shorter than k * item_len")
+    if branches.numel() * branches.element_size() < list_branch_bytes(n, item_len) * k:
+        raise ValueError("branch buffer smaller than k records")
+    if roots.numel() * roots.element_size() < (32 * k if root_stride else 32):
+        raise ValueError("root buffer too small")
+    if out is None:
+        out = torch.empty(k, dtype=torch.uint8, device=branches.device)
+    clen = container.numel() * container.element_size() if container is not None else 0
+    _lib.invoke("mk_dev_verify_list_branches", _p(values), _p(indices), k, n, item_len, _p(branches), _p(roots),
+                root_stride, _p(container) if container is not None else None, clen, container_off, _p(out),
+                _stream(branches.device), device=dev)
+    return out
+
+
 def struct_list_tree_build_workspace_bytes(n: int, spec) -> int:
     from .registry import _fields
 

@@ -53,6 +53,7 @@ class _Tree:
     _noun = ""      # what a value is called in messages
     _one = ""       # ValueError text of update(): "one ... per index"
     _reader = ""    # name of the read-back entry point and method
+    _leaf32 = False  # level 0 is a 32-B root / digest per value, not the value itself
 
     def __init__(self, value_len: int, *new_args, device: int = -1):
         self._len = int(value_len)
@@ -133,6 +134,54 @@ class _Tree:
         self._call(self._reader, first, count, _ptr(out))
         return out
 
+    def branches(self, indices):
+        """Merkle proofs of the values at ``indices`` (any order, repeats
+        allowed; an index >= len(self) raises): ``(values, branches)``, the
+        (k, leaf_len) level-0 values -- the items of a ListTree, the 32-B struct
+        roots / element digests of the other two -- and the (k, stride) proof
+        records that ``verify_branches`` takes with ``root()``.
+        One upload of the indices, one launch, one read-back."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        leaf = 32 if self._leaf32 else self._len
+        stride = int(_lib.load().mk_ssz_list_branch_bytes(len(self), leaf))
+        values = np.zeros((idx.size, leaf), dtype=np.uint8)
+        out = np.zeros((idx.size, stride), dtype=np.uint8)
+        self._call("branches", _ptr(idx), idx.size, _ptr(values), _ptr(out))
+        return values, out
+
+
+def verify_branches(values, indices, n: int, item_len: int, branches, root, container=None,
+                    container_off: int = None, device: int = -1) -> np.ndarray:
+    """Verify list-tree proofs from host buffers on the GPU
+    (mk_verify_list_branches): a bool array, True where ``values[g]`` at index
+    ``indices[g]`` of a list of ``n`` ``item_len``-byte leaves folds through
+    ``branches[g]`` to ``root`` -- one 32-byte root for the batch, or one per
+    proof.  With ``container`` (the message ``TreeSet.branches`` returns) the
+    list root is substituted at ``container_off`` and the hash of the message
+    is what is compared (``TreeSet.root()``)."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    k = idx.size
+    vals = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1)
+    br = np.ascontiguousarray(branches, dtype=np.uint8).reshape(-1)
+    roots = np.frombuffer(bytes(root), dtype=np.uint8) if isinstance(root, (bytes, bytearray)) else \
+        np.ascontiguousarray(root, dtype=np.uint8).reshape(-1)
+    stride = int(_lib.load().mk_ssz_list_branch_bytes(n, item_len))
+    if vals.size != k * item_len or br.size != k * stride:
+        raise ValueError("one item_len-byte value and one proof record per index")
+    if roots.size not in (32, 32 * k):
+        raise ValueError("one 32-byte root, or one per proof")
+    root_stride = 32 if (roots.size == 32 * k and k != 1) else 0
+    cont = None
+    if container is not None and len(container):
+        if container_off is None:
+            raise ValueError("a container needs the tree's container_off")
+        cont = np.frombuffer(bytes(container), dtype=np.uint8)
+    ok = np.zeros(k, dtype=np.uint8)
+    _lib.invoke("mk_verify_list_branches", _ptr(vals), _ptr(idx), k, int(n), int(item_len), _ptr(br), _ptr(roots),
+                root_stride, _ptr(cont) if cont is not None else None, cont.size if cont is not None else 0,
+                int(container_off or 0), _ptr(ok), device=device)
+    return ok.astype(bool)
+
 
 class ListTree(_Tree):
     """A list of fixed-length items and its merkleHash tree, device-resident."""
@@ -151,6 +200,7 @@ class StructListTree(_Tree):
     device-resident: records, struct roots and levels."""
 
     _prefix, _noun, _one, _reader = "struct_list_tree", "records", "one record per index", "records"
+    _leaf32 = True
     records = _Tree._read
 
     def __init__(self, record_len: int, fields, capacity: int = 0, device: int = -1):
@@ -170,6 +220,7 @@ class BytesListTree(_Tree):
     levels."""
 
     _prefix, _noun, _one, _reader = "bytes_list_tree", "elements", "one elem_len-byte element per index", "elems"
+    _leaf32 = True
     elems = _Tree._read
 
     def __init__(self, elem_len: int, capacity: int = 0, device: int = -1):
@@ -200,6 +251,8 @@ class TreeSet:
         self._device = device
         self._handle = None
         self._len = []  # value length of every tree
+        self._leaf = []  # length of its level-0 entries: the value's (a list tree) or 32
+        self._coff = []  # where its root goes in the message (None: nowhere)
         h = ctypes.c_void_p()
         _lib.invoke("mk_tree_set_new", self.container_len, ctypes.byref(h), device=device)
         self._handle = h
@@ -242,6 +295,8 @@ class TreeSet:
         self._call("add", int(kind), int(value_len), _fields(spec) if fields is not None else None, len(spec),
                    int(capacity), off, ctypes.byref(out))
         self._len.append(int(value_len))
+        self._leaf.append(int(value_len) if int(kind) == _lib.MK_TREE_LIST else 32)
+        self._coff.append(None if container_off is None else int(container_off))
         return int(out.value)
 
     def put(self, off: int, data) -> None:
@@ -308,3 +363,30 @@ class TreeSet:
         out = np.empty((max(count, 0), self._len[tree]), dtype=np.uint8)
         self._call("items", tree, first, count, _ptr(out))
         return out
+
+    def leaf_len(self, tree) -> int:
+        """Bytes of a level-0 entry of a tree: what ``branches`` proves."""
+        return self._leaf[self._tree(tree)]
+
+    def container_off(self, tree):
+        """Where a tree's root lies in the message (None: it is no field of it)."""
+        return self._coff[self._tree(tree)]
+
+    def branches(self, tree, indices):
+        """Merkle proofs of the values at ``indices`` of one tree, whatever is
+        pending flushed first as ``root()`` does: ``(values, branches,
+        container)`` -- ``_Tree.branches``' pair and the hash message with
+        every tree's root in place (b"" for a set without a container).
+        ``verify_branches(values, indices, count(tree), leaf_len(tree),
+        branches, root(), container, container_off(tree))`` checks them against
+        the root of the whole struct; a tree that is no field of the container
+        verifies against ``tree_root(tree)`` with no container."""
+        tree = self._tree(tree)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        leaf = self._leaf[tree]
+        stride = int(_lib.load().mk_ssz_list_branch_bytes(self.count(tree), leaf))
+        values = np.zeros((idx.size, leaf), dtype=np.uint8)
+        out = np.zeros((idx.size, stride), dtype=np.uint8)
+        msg = np.zeros(self.container_len, dtype=np.uint8)
+        self._call("branches", tree, _ptr(idx), idx.size, _ptr(values), _ptr(out), _ptr(msg))
+        return values, out, msg.tobytes()
