@@ -818,6 +818,84 @@ int mk_tree_set_items(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t fir
 int mk_tree_set_branches(mk_call* call, mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k,
                          uint8_t* values_out, uint8_t* branches_out, uint8_t* container_out);
 
+/* ---- resident trees copied on the device: clone, copy, reserve --- */
+/* A second resident state (the candidate post-state of a block, the other side
+ * of a fork) and a tree moved to a larger capacity are one operation: the live
+ * part of a tree moves from the layout of one capacity into the layout of
+ * another and nothing is hashed.  The live part is the n values (n x item_len
+ * bytes), level 0 of a STRUCT / BYTES tree (32 n bytes), the ceil(nchunks /
+ * 2^d) nodes of every stored level d = 1 .. D -- from node sum_{1<=i<d}
+ * ceil(cap_chunks / 2^i) of the source's level array to the same sum for the
+ * destination's capacity -- and the 32-byte root.  Levels above D and nodes
+ * beyond a level's count are unspecified in both layouts: they are not read
+ * and not written, so the destination is a valid tree of n values of capacity
+ * dst_capacity whatever its buffers held before, and what a shrink left to the
+ * right of the source's end does not travel.
+ * mk_dev_ssz_trees_copy copies up to MK_TREES_MAX trees and one optional 32-byte
+ * extra (a set's container root; both pointers NULL: none) in ONE launch.
+ * `trees` is host memory, read only during the call: the descriptors travel as
+ * kernel arguments.  Uploads nothing, allocates nothing, needs no workspace,
+ * never synchronises and can be captured into a hipGraph.  d_*_items at any
+ * byte alignment (a 16-B aligned pair moves in 16-B pieces); d_*_level0 (NULL
+ * for MK_TREE_LIST), d_*_levels, d_*_root32 and the extra 16-B aligned.
+ * MK_EINVAL, every check before a device is looked up and nothing launched:
+ * ntrees > MK_TREES_MAX, an unknown kind, item_len == 0 or above 2^30, n above
+ * either capacity, capacity * item_len overflowing, a null pointer where the
+ * shape needs one (values and level 0 for n > 0, levels for D >= 1, the roots
+ * always), a level 0 given for a list tree, a misaligned level 0, level array,
+ * root or extra, an extra with one side NULL, and a source range that overlaps
+ * a destination range of the same call (a tree's levels count from the first
+ * stored node to the top).  ntrees == 0 without an extra is MK_OK and launches
+ * nothing.  Source and destination lie on the stream's device. */
+typedef struct mk_tree_copy {
+    uint32_t kind, item_len;          /* MK_TREE_LIST / _STRUCT / _BYTES; item / record / element length */
+    uint64_t n, src_capacity, dst_capacity;
+    const void *d_src_items, *d_src_level0, *d_src_levels, *d_src_root32;
+    void *d_dst_items, *d_dst_level0, *d_dst_levels, *d_dst_root32;
+} mk_tree_copy;
+int mk_dev_ssz_trees_copy(mk_call* call, const mk_tree_copy* trees, uint32_t ntrees, const void* d_src_extra32,
+                          void* d_dst_extra32, void* stream);
+/* Handle forms, the same for the three kinds.
+ * clone: a new handle of the source's kind, item length, record layout, device
+ *   and capacity holding the source's list: one copy launch, nothing uploaded,
+ *   nothing hashed.  The two handles share nothing afterwards.
+ * copy: dst becomes a copy of src.  dst must be of the same kind, item length
+ *   and record layout and on the same device, else MK_EINVAL and nothing
+ *   changes.  dst keeps its capacity when src's count fits; otherwise it gets
+ *   buffers of src's capacity, allocated before anything is enqueued, so a
+ *   failed allocation leaves dst as it was.  dst == src is MK_OK and does nothing.
+ * reserve: room for `capacity` values; capacity <= the current one is a no-op.
+ *   Allocates the new buffers, moves the tree into the new layout by one copy
+ *   launch and frees the old ones: root, count and values are unchanged and
+ *   nothing is hashed (an append past the capacity still doubles and rebuilds).
+ * capacity: the values the handle has room for (0 for NULL). */
+int mk_list_tree_clone(mk_call* call, mk_list_tree* src, mk_list_tree** out);
+int mk_list_tree_copy(mk_call* call, mk_list_tree* dst, mk_list_tree* src);
+int mk_list_tree_reserve(mk_call* call, mk_list_tree* t, uint64_t capacity);
+uint64_t mk_list_tree_capacity(const mk_list_tree* t);
+int mk_struct_list_tree_clone(mk_call* call, mk_struct_list_tree* src, mk_struct_list_tree** out);
+int mk_struct_list_tree_copy(mk_call* call, mk_struct_list_tree* dst, mk_struct_list_tree* src);
+int mk_struct_list_tree_reserve(mk_call* call, mk_struct_list_tree* t, uint64_t capacity);
+uint64_t mk_struct_list_tree_capacity(const mk_struct_list_tree* t);
+int mk_bytes_list_tree_clone(mk_call* call, mk_bytes_list_tree* src, mk_bytes_list_tree** out);
+int mk_bytes_list_tree_copy(mk_call* call, mk_bytes_list_tree* dst, mk_bytes_list_tree* src);
+int mk_bytes_list_tree_reserve(mk_call* call, mk_bytes_list_tree* t, uint64_t capacity);
+uint64_t mk_bytes_list_tree_capacity(const mk_bytes_list_tree* t);
+/* The same for a set.  clone / copy flush the source first, as root does, so
+ * the copy holds what root() would describe; then ONE copy launch moves every
+ * tree and the container root, and the hash message is copied on the host.
+ * The destination's pending changes are dropped and it is not dirty afterwards.
+ * copy: the sets must agree in container length, device and, tree by tree, in
+ * kind, item length, record layout and container offset, else MK_EINVAL and
+ * nothing changes; every destination tree that is too small gets its new
+ * buffers before anything is enqueued; dst == src is MK_OK and does nothing.
+ * reserve / capacity: mk_*_tree_reserve / _capacity of one tree of the set
+ * (pending changes stay pending; capacity is 0 for a tree the set has not). */
+int mk_tree_set_clone(mk_call* call, mk_tree_set* src, mk_tree_set** out);
+int mk_tree_set_copy(mk_call* call, mk_tree_set* dst, mk_tree_set* src);
+int mk_tree_set_reserve(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t capacity);
+uint64_t mk_tree_set_capacity(const mk_tree_set* s, uint32_t tree);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

@@ -196,6 +196,23 @@ _SIGS = {
     "mk_struct_list_tree_branches": (_int, [_cp, _vp, _vp, _u64, _vp, _vp]),
     "mk_bytes_list_tree_branches": (_int, [_cp, _vp, _vp, _u64, _vp, _vp]),
     "mk_tree_set_branches": (_int, [_cp, _vp, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "mk_dev_ssz_trees_copy": (_int, [_cp, _vp, _u32, _vp, _vp, _vp]),
+    "mk_list_tree_clone": (_int, [_cp, _vp, _vp]),
+    "mk_list_tree_copy": (_int, [_cp, _vp, _vp]),
+    "mk_list_tree_reserve": (_int, [_cp, _vp, _u64]),
+    "mk_list_tree_capacity": (_u64, [_vp]),
+    "mk_struct_list_tree_clone": (_int, [_cp, _vp, _vp]),
+    "mk_struct_list_tree_copy": (_int, [_cp, _vp, _vp]),
+    "mk_struct_list_tree_reserve": (_int, [_cp, _vp, _u64]),
+    "mk_struct_list_tree_capacity": (_u64, [_vp]),
+    "mk_bytes_list_tree_clone": (_int, [_cp, _vp, _vp]),
+    "mk_bytes_list_tree_copy": (_int, [_cp, _vp, _vp]),
+    "mk_bytes_list_tree_reserve": (_int, [_cp, _vp, _u64]),
+    "mk_bytes_list_tree_capacity": (_u64, [_vp]),
+    "mk_tree_set_clone": (_int, [_cp, _vp, _vp]),
+    "mk_tree_set_copy": (_int, [_cp, _vp, _vp]),
+    "mk_tree_set_reserve": (_int, [_cp, _vp, _u32, _u64]),
+    "mk_tree_set_capacity": (_u64, [_vp, _u32]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),
@@ -231,6 +248,13 @@ class TreeUpdate(ctypes.Structure):
     _fields_ = [("kind", _u32), ("item_len", _u32), ("d_items", _vp), ("d_level0", _vp), ("d_levels", _vp),
                 ("n_old", _u64), ("n_new", _u64), ("capacity", _u64), ("d_idx", _vp), ("k_idx", _u64),
                 ("d_values", _vp), ("fields", _vp), ("nfields", _u32), ("container_off", _u32), ("d_root32", _vp)]
+
+
+class TreeCopy(ctypes.Structure):
+    """mk_tree_copy: one tree of mk_dev_ssz_trees_copy."""
+    _fields_ = [("kind", _u32), ("item_len", _u32), ("n", _u64), ("src_capacity", _u64), ("dst_capacity", _u64),
+                ("d_src_items", _vp), ("d_src_level0", _vp), ("d_src_levels", _vp), ("d_src_root32", _vp),
+                ("d_dst_items", _vp), ("d_dst_level0", _vp), ("d_dst_levels", _vp), ("d_dst_root32", _vp)]
 
 
 _lib = None

@@ -71,6 +71,9 @@ const TreeKind kBytesKind = {
         return dev_update(t.items.p, n_old, n_new, t.cap, t.item_len, t.level0.p, t.levels.p, d_idx, k_idx, d_values,
                           t.root.p, t.ws.p, st);
     },
+    MK_TREE_BYTES,
+    [](const TreeHandle&) -> TreeHandle* { return new (std::nothrow) mk_bytes_list_tree(); },
+    [](const TreeHandle&, const TreeHandle&) { return true; },
 };
 
 }  // namespace
@@ -244,5 +247,25 @@ int mk_bytes_list_tree_branches(mk_call* call, mk_bytes_list_tree* t, const uint
     Scope S(call);
     return S.done(tree_branches(t, idx, k, values_out, branches_out));
 }
+
+int mk_bytes_list_tree_clone(mk_call* call, mk_bytes_list_tree* src, mk_bytes_list_tree** out) {
+    Scope S(call);
+    TreeHandle* t = nullptr;
+    const int rc = out ? tree_clone(src, &t) : fail(MK_EINVAL, "null pointer");
+    if (out) *out = static_cast<mk_bytes_list_tree*>(t);
+    return S.done(rc);
+}
+
+int mk_bytes_list_tree_copy(mk_call* call, mk_bytes_list_tree* dst, mk_bytes_list_tree* src) {
+    Scope S(call);
+    return S.done(tree_copy(dst, src));
+}
+
+int mk_bytes_list_tree_reserve(mk_call* call, mk_bytes_list_tree* t, uint64_t capacity) {
+    Scope S(call);
+    return S.done(tree_reserve(t, capacity));
+}
+
+uint64_t mk_bytes_list_tree_capacity(const mk_bytes_list_tree* t) { return t ? t->cap : 0; }
 
 }  // extern "C"

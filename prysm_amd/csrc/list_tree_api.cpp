@@ -107,6 +107,9 @@ const TreeKind kListKind = {
         return dev_update(t.items.p, n_old, n_new, t.cap, t.item_len, t.levels.p, d_idx, k_idx, d_values, t.root.p,
                           t.ws.p, st);
     },
+    MK_TREE_LIST,
+    [](const TreeHandle&) -> TreeHandle* { return new (std::nothrow) mk_list_tree(); },
+    [](const TreeHandle&, const TreeHandle&) { return true; },
 };
 
 }  // namespace
@@ -408,5 +411,25 @@ int mk_list_tree_branches(mk_call* call, mk_list_tree* t, const uint64_t* idx, u
     Scope S(call);
     return S.done(tree_branches(t, idx, k, values_out, branches_out));
 }
+
+int mk_list_tree_clone(mk_call* call, mk_list_tree* src, mk_list_tree** out) {
+    Scope S(call);
+    TreeHandle* t = nullptr;
+    const int rc = out ? tree_clone(src, &t) : fail(MK_EINVAL, "null pointer");
+    if (out) *out = static_cast<mk_list_tree*>(t);
+    return S.done(rc);
+}
+
+int mk_list_tree_copy(mk_call* call, mk_list_tree* dst, mk_list_tree* src) {
+    Scope S(call);
+    return S.done(tree_copy(dst, src));
+}
+
+int mk_list_tree_reserve(mk_call* call, mk_list_tree* t, uint64_t capacity) {
+    Scope S(call);
+    return S.done(tree_reserve(t, capacity));
+}
+
+uint64_t mk_list_tree_capacity(const mk_list_tree* t) { return t ? t->cap : 0; }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include "list_branch.hpp"
 #include "merkle_kernels.hpp"
 #include "tree_compact.hpp"
+#include "tree_copy.hpp"
 
 namespace mk {
 
@@ -4857,6 +4858,122 @@ __global__ __launch_bounds__(64 * kBranchWaves) void k_list_tree_branches(
                 if (branch_sibling(b, j, d, &node)) v = levels[2 * (lvoff[d] + node) + h];
             }
             out[(uint64_t)pieces * g + q] = v;
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------
+// Copy of resident trees between the layouts of two capacities (DESIGN.md
+// §5m): the live part of up to kTreesMax trees and one 32-byte extra, cut into
+// 16-byte pieces by tree_copy.hpp; nothing is hashed.  The pieces of the whole
+// call are numbered through, tree after tree, and a bounded grid strides over
+// them: a thread issues the loads of kCopyUnroll pieces, kCopyThreads apart (a
+// wave's load is 1 KiB contiguous inside a segment), then their stores.  Where
+// a tree's pieces start, where each of its segments starts and the two base
+// addresses of every segment -- the level offsets of the two layouts in them --
+// are per-workgroup LDS, filled by one wave per tree, a lane per segment.  A
+// piece of the values whose addresses are not 16-byte aligned, or the short
+// last one, goes in units of 8, 4 or 1 bytes and only as far as the segment
+// reaches; level 0, the levels and the roots are 16-byte aligned by contract.
+// Every thread writes only its own pieces: no counter, no hand-off, no workspace.
+__device__ __forceinline__ void copy_units(uint8_t* dst, const uint8_t* src, uint32_t valid) {
+    const uintptr_t a = (uintptr_t)dst | (uintptr_t)src;
+    uint32_t i = 0;
+    if ((a & 7u) == 0)
+        for (; i + 8 <= valid; i += 8) *reinterpret_cast<uint64_t*>(dst + i) = *reinterpret_cast<const uint64_t*>(src + i);
+    if ((a & 3u) == 0)
+        for (; i + 4 <= valid; i += 4) *reinterpret_cast<uint32_t*>(dst + i) = *reinterpret_cast<const uint32_t*>(src + i);
+    for (; i < valid; ++i) dst[i] = src[i];
+}
+
+// a 16-byte piece in registers, and HBM named as such: an address read back from LDS is otherwise a flat one
+typedef uint32_t copy_u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) copy_u32x4 copy_global_u32x4;
+
+__global__ __launch_bounds__(kCopyThreads) void k_trees_copy(TreesCopyArgs g) {
+    __shared__ CopyShape shp[kTreesMax];
+    __shared__ uint64_t tfirst[kTreesMax + 1];                // the call's first piece of tree t; [ntrees]: the extra's
+    __shared__ uint64_t sfirst[kTreesMax][kCopySegsMax + 1];  // tree t's first piece of segment s; [segs]: its total
+    __shared__ const uint8_t* ssrc[kTreesMax][kCopySegsMax];  // where segment s starts in the source ...
+    __shared__ uint8_t* sdst[kTreesMax][kCopySegsMax];        // ... and in the destination
+    const uint32_t nt = g.ntrees < kTreesMax ? g.ntrees : kTreesMax;
+    const uint32_t w = threadIdx.x >> 6, L = threadIdx.x & 63u;
+    for (uint32_t t0 = 0; t0 < nt; t0 += kCopyThreads / 64) {
+        const uint32_t t = __builtin_amdgcn_readfirstlane(t0 + w);  // wave-uniform: the descriptor by scalar loads
+        if (t >= nt) continue;
+        const CopyTree& T = g.t[t];
+        const CopyShape c = copy_shape(T.n, T.cap_src, T.cap_dst, T.item_len, T.level0 != 0);
+        if (L == 0) shp[t] = c;
+        const uint32_t segs = copy_segs(c);
+        for (uint32_t s = L; s <= segs; s += 64) {
+            sfirst[t][s] = copy_seg_first(c, s);
+            if (s == segs) break;
+            uint64_t so, dof;
+            copy_seg_offs(c, s, &so, &dof);
+            const uint32_t b = copy_seg_buf(c, s);
+            const uint8_t* sp = b == kCopyItems    ? T.src_items
+                                : b == kCopyLevel0 ? T.src_level0
+                                : b == kCopyLevels ? T.src_levels
+                                                   : T.src_root;
+            uint8_t* dp = b == kCopyItems    ? T.dst_items
+                          : b == kCopyLevel0 ? T.dst_level0
+                          : b == kCopyLevels ? T.dst_levels
+                                             : T.dst_root;
+            ssrc[t][s] = sp + so;
+            sdst[t][s] = dp + dof;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t a = 0;
+        for (uint32_t t = 0; t < nt; ++t) {
+            tfirst[t] = a;
+            a += sfirst[t][copy_segs(shp[t])];
+        }
+        tfirst[nt] = a;
+    }
+    __syncthreads();
+    const uint64_t in_trees = tfirst[nt], total = in_trees + (g.extra_dst ? 32 / kCopyPiece : 0);
+    const uint64_t turn = (uint64_t)kCopyThreads * kCopyUnroll;
+    for (uint64_t base = blockIdx.x * turn; base < total; base += gridDim.x * turn) {
+        copy_u32x4 v[kCopyUnroll];
+        const uint8_t* sp[kCopyUnroll];
+        uint8_t* dp[kCopyUnroll];
+        uint32_t valid[kCopyUnroll];
+        bool whole[kCopyUnroll];
+#pragma unroll
+        for (uint32_t u = 0; u < kCopyUnroll; ++u) {
+            const uint64_t p = base + u * kCopyThreads + threadIdx.x;
+            valid[u] = 0;
+            sp[u] = nullptr;
+            dp[u] = nullptr;
+            if (p >= total) {
+            } else if (p >= in_trees) {
+                sp[u] = g.extra_src + kCopyPiece * (p - in_trees);
+                dp[u] = g.extra_dst + kCopyPiece * (p - in_trees);
+                valid[u] = kCopyPiece;
+            } else {
+                uint32_t t = 0, s = 0;
+                while (p >= tfirst[t + 1]) ++t;  // p < tfirst[nt]
+                const uint64_t q = p - tfirst[t];
+                while (q >= sfirst[t][s + 1]) ++s;  // q < sfirst[t][segs]; an empty segment is stepped over
+                const CopyPiece pc = copy_piece_in(shp[t], s, q - sfirst[t][s], 0, 0);
+                sp[u] = ssrc[t][s] + pc.src_off;
+                dp[u] = sdst[t][s] + pc.dst_off;
+                valid[u] = pc.valid;
+            }
+            whole[u] = valid[u] == kCopyPiece && (((uintptr_t)sp[u] | (uintptr_t)dp[u]) & 15u) == 0;
+            v[u] = copy_u32x4{0u, 0u, 0u, 0u};
+            if (whole[u]) v[u] = *reinterpret_cast<const copy_global_u32x4*>((uintptr_t)sp[u]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kCopyUnroll; ++u) {
+            if (whole[u]) *reinterpret_cast<copy_global_u32x4*>((uintptr_t)dp[u]) = v[u];
+        }
+        // the pieces that go in smaller units, apart: the stores above wait for their own loads only
+#pragma unroll
+        for (uint32_t u = 0; u < kCopyUnroll; ++u) {
+            if (!whole[u] && valid[u]) copy_units(dp[u], sp[u], valid[u]);
         }
     }
 }

@@ -264,4 +264,25 @@ __global__ void k_verify_list_branches(const uint8_t* values, const uint64_t* in
                                        uint32_t root_stride, const uint8_t* container, uint32_t container_len,
                                        uint32_t container_off, uint8_t* ok);
 
+// Copy of up to kTreesMax resident trees from the layout of one capacity into that of another, plus one
+// optional 32-byte extra (tree_copy_api.cpp; the piece map: tree_copy.hpp).  The descriptors
+// by value, 1.6 KB of kernel arguments: nothing is uploaded.
+struct CopyTree {
+    const uint8_t *src_items, *src_level0, *src_levels, *src_root;  // level0, levels and root 16-B aligned
+    uint8_t *dst_items, *dst_level0, *dst_levels, *dst_root;
+    uint64_t n, cap_src, cap_dst;
+    uint32_t item_len;
+    uint32_t level0;  // a struct / bytes tree: 32 n bytes of level 0 travel
+};
+struct TreesCopyArgs {
+    CopyTree t[kTreesMax];
+    const uint8_t* extra_src;  // 32 bytes, 16-B aligned; NULL: none
+    uint8_t* extra_dst;
+    uint32_t ntrees;
+};
+constexpr uint32_t kCopyThreads = 256;  // a workgroup
+constexpr uint32_t kCopyUnroll = 4;     // 16-byte pieces a thread has in flight per turn
+// a bounded grid striding over the 16-byte pieces of all the trees; every thread writes only its own pieces
+__global__ void k_trees_copy(TreesCopyArgs g);
+
 }  // namespace mk

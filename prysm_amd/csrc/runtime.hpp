@@ -226,6 +226,9 @@ struct TreeKind {
     int (*dev_build)(const TreeHandle& t, uint64_t n, hipStream_t st);
     int (*dev_update)(const TreeHandle& t, uint64_t n_old, uint64_t n_new, const uint64_t* d_idx, uint64_t k_idx,
                       const void* d_values, hipStream_t st);
+    uint32_t id;                                                  // MK_TREE_LIST / _STRUCT / _BYTES
+    TreeHandle* (*make_like)(const TreeHandle& t);                // an empty handle of t's type and layout (null: no memory)
+    bool (*same_layout)(const TreeHandle& a, const TreeHandle& b);  // two handles of this kind: the same record layout
 };
 struct TreeHandle {
     const TreeKind* kind = nullptr;
@@ -250,6 +253,26 @@ int tree_read(TreeHandle* t, uint64_t first, uint64_t cnt, uint8_t* out);
 // Merkle proofs of the k values at idx (any order, repeats allowed): the k level-0 values
 // (items, struct roots, element digests) and the k records; one upload, one launch, one read-back
 int tree_branches(TreeHandle* t, const uint64_t* idx, uint64_t k, uint8_t* values_out, uint8_t* branches_out);
+// Clone, copy and reserve: a tree moved between the layouts of two capacities by the copy
+// launch (tree_copy_api.cpp); nothing is hashed.  tree_clone: a new handle like src holding its list;
+// tree_copy: dst becomes a copy of src (the same kind, item length, layout and device, else MK_EINVAL);
+// tree_reserve: room for `capacity` values.
+int tree_clone(TreeHandle* src, TreeHandle** out);
+int tree_copy(TreeHandle* dst, TreeHandle* src);
+int tree_reserve(TreeHandle* t, uint64_t capacity);
+// The pieces of those, for a set that moves all its trees in one launch (tree_set_api.cpp).  The caller
+// holds the locks and has the device bound.
+struct TreeBufs {  // what of a tree depends on its capacity, and optionally a root
+    DevBuf items, level0, levels, root;
+};
+bool tree_same_shape(const TreeHandle& a, const TreeHandle& b);  // kind, item length, record layout
+int tree_bufs_alloc(const TreeHandle& like, uint64_t cap, bool with_root, TreeBufs& b);  // frees what it got on failure
+void tree_bufs_free(TreeBufs& b);
+void tree_bufs_install(TreeHandle* t, TreeBufs& b, uint64_t cap);  // t's old buffers are freed (after a synchronise)
+// a handle like src (buffers of src's capacity and a root, nothing built: the copy writes every live byte), count 0
+int tree_new_like(const TreeHandle& src, TreeHandle** out);
+// src's live part into dst's buffers, or into nb (of dst_cap values, dst's root where nb has none)
+mk_tree_copy tree_copy_desc(const TreeHandle& src, const TreeHandle& dst, const TreeBufs* nb, uint64_t dst_cap);
 // each kind's TreeKind and an empty handle of its type for tree_new (null: the allocation failed)
 const TreeKind& list_tree_kind();
 const TreeKind& struct_tree_kind();
@@ -284,6 +307,12 @@ int list_branches_check(const void* d_level0, uint64_t n, uint64_t capacity, uin
                         const uint64_t* d_idx, uint64_t k, const void* d_branches);
 int list_branches_launch(const void* d_level0, uint64_t n, uint64_t capacity, uint32_t item_len, const void* d_levels,
                          const uint64_t* d_idx, uint64_t k, void* d_branches, hipStream_t st);
+
+// ---- resident trees copied on the device (tree_copy_api.cpp) ----------------------
+// mk_dev_ssz_trees_copy: every argument check (no device needed), then the one launch on st
+int trees_copy_check(const mk_tree_copy* trees, uint32_t ntrees, const void* d_src_extra32, const void* d_dst_extra32);
+int trees_copy_launch(const mk_tree_copy* trees, uint32_t ntrees, const void* d_src_extra32, void* d_dst_extra32,
+                      hipStream_t st);
 
 // ---- several trees in one call (tree_many_api.cpp) ------------------------------------------
 // mk_ssz_trees_update_workspace_bytes with its error, and mk_dev_ssz_trees_update

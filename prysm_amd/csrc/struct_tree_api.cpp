@@ -97,6 +97,13 @@ const TreeKind kStructKind = {
         return dev_update(layout_of(t), t.items.p, n_old, n_new, t.cap, t.level0.p, t.levels.p, d_idx, k_idx,
                           d_values, t.root.p, t.ws.p, st);
     },
+    MK_TREE_STRUCT,
+    [](const TreeHandle& t) { return struct_tree_handle(layout_of(t)); },
+    [](const TreeHandle& a, const TreeHandle& b) {  // the parsed spec keeps every entry as it was given, zeros behind
+        const mk::HostSpec &x = layout_of(a).sp, &y = layout_of(b).sp;
+        return x.nfields == y.nfields && !std::memcmp(x.kind, y.kind, sizeof x.kind) &&
+               !std::memcmp(x.off, y.off, sizeof x.off) && !std::memcmp(x.len, y.len, sizeof x.len);
+    },
 };
 
 }  // namespace
@@ -344,5 +351,25 @@ int mk_struct_list_tree_branches(mk_call* call, mk_struct_list_tree* t, const ui
     Scope S(call);
     return S.done(tree_branches(t, idx, k, values_out, branches_out));
 }
+
+int mk_struct_list_tree_clone(mk_call* call, mk_struct_list_tree* src, mk_struct_list_tree** out) {
+    Scope S(call);
+    TreeHandle* t = nullptr;
+    const int rc = out ? tree_clone(src, &t) : fail(MK_EINVAL, "null pointer");
+    if (out) *out = static_cast<mk_struct_list_tree*>(t);
+    return S.done(rc);
+}
+
+int mk_struct_list_tree_copy(mk_call* call, mk_struct_list_tree* dst, mk_struct_list_tree* src) {
+    Scope S(call);
+    return S.done(tree_copy(dst, src));
+}
+
+int mk_struct_list_tree_reserve(mk_call* call, mk_struct_list_tree* t, uint64_t capacity) {
+    Scope S(call);
+    return S.done(tree_reserve(t, capacity));
+}
+
+uint64_t mk_struct_list_tree_capacity(const mk_struct_list_tree* t) { return t ? t->cap : 0; }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 // list, its level 0 and its levels in HBM, assign / update / append / root /
 // read-back under one mutex.  What a kind does differently is its TreeKind
 // (runtime.hpp), defined in list_tree_api, struct_tree_api, bytes_tree_api.
+#include <functional>
+
 #include "list_branch.hpp"
 #include "runtime.hpp"
 
@@ -278,6 +280,152 @@ int tree_branches(TreeHandle* t, const uint64_t* idx, uint64_t k, uint8_t* value
     const BranchShape b = branch_shape(t->count, t->cap, L);
     for (uint64_t g = 0; g < k; ++g)
         std::memcpy(values_out + g * L, branches_out + g * stride + branch_item_pos(b, idx[g]), L);
+    return MK_OK;
+}
+
+// ---- clone, copy, reserve ---------------------------------------------------------
+// One operation under the three: the live part of a tree moved from the layout
+// of one capacity into buffers laid out for another by the copy launch
+// (tree_copy_api.cpp).  Nothing is uploaded and nothing is hashed.
+bool tree_same_shape(const TreeHandle& a, const TreeHandle& b) {
+    return a.kind == b.kind && a.item_len == b.item_len && a.kind->same_layout(a, b);
+}
+
+void tree_bufs_free(TreeBufs& b) {
+    for (DevBuf* d : {&b.items, &b.level0, &b.levels, &b.root}) {
+        if (d->p) (void)hipFree(d->p);
+        *d = DevBuf{};
+    }
+}
+
+// the sizes of alloc() / grow_levels() above
+int tree_bufs_alloc(const TreeHandle& like, uint64_t cap, bool with_root, TreeBufs& b) {
+    const uint32_t L = like.item_len;
+    int rc = like.kind->check_shape(0, cap, L);
+    if (!rc) rc = grow(b.items, cap * L + 16);
+    if (!rc && like.kind->level0) rc = grow(b.level0, 32 * cap + 16);
+    if (!rc) rc = grow(b.levels, mk_ssz_list_tree_levels_bytes(cap, like.kind->level0 ? 32 : L));
+    if (!rc && with_root) rc = grow(b.root, 32);
+    if (rc) tree_bufs_free(b);
+    return rc;
+}
+
+void tree_bufs_install(TreeHandle* t, TreeBufs& b, uint64_t cap) {
+    TreeBufs old;
+    old.items = t->items, old.level0 = t->level0, old.levels = t->levels;
+    t->items = b.items, t->level0 = b.level0, t->levels = b.levels;
+    if (b.root.p) {
+        old.root = t->root;
+        t->root = b.root;
+    }
+    t->cap = cap;
+    b = TreeBufs{};
+    tree_bufs_free(old);
+}
+
+int tree_new_like(const TreeHandle& src, TreeHandle** out) {
+    TreeHandle* t = src.kind->make_like(src);
+    if (!t) return fail(MK_ENOMEM, "%s allocation failed", src.kind->name);
+    t->kind = src.kind;
+    t->dev = src.dev;
+    t->item_len = src.item_len;
+    TreeBufs b;
+    const int rc = tree_bufs_alloc(src, src.cap, true, b);
+    if (rc) {
+        tree_free(t);
+        return rc;
+    }
+    tree_bufs_install(t, b, src.cap);
+    *out = t;
+    return MK_OK;
+}
+
+mk_tree_copy tree_copy_desc(const TreeHandle& src, const TreeHandle& dst, const TreeBufs* nb, uint64_t dst_cap) {
+    mk_tree_copy c{};
+    c.kind = src.kind->id;
+    c.item_len = src.item_len;
+    c.n = src.count;
+    c.src_capacity = src.cap;
+    c.dst_capacity = dst_cap;
+    const bool l0 = src.kind->level0;
+    c.d_src_items = src.items.p, c.d_src_level0 = l0 ? src.level0.p : nullptr, c.d_src_levels = src.levels.p;
+    c.d_src_root32 = src.root.p;
+    c.d_dst_items = nb ? nb->items.p : dst.items.p;
+    c.d_dst_level0 = !l0 ? nullptr : nb ? nb->level0.p : dst.level0.p;
+    c.d_dst_levels = nb ? nb->levels.p : dst.levels.p;
+    c.d_dst_root32 = nb && nb->root.p ? nb->root.p : dst.root.p;
+    return c;
+}
+
+namespace {
+// one tree's copy: the checks, the launch, the synchronise
+int copy_one(const mk_tree_copy& c, hipStream_t st) {
+    TRY(trees_copy_check(&c, 1, nullptr, nullptr));
+    TRY(trees_copy_launch(&c, 1, nullptr, nullptr, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MK_OK;
+}
+}  // namespace
+
+int tree_clone(TreeHandle* src, TreeHandle** out) {
+    if (!src || !out) return fail(MK_EINVAL, "null pointer");
+    *out = nullptr;
+    std::lock_guard<std::mutex> tl(src->mu);
+    TRY(bind_dev(src->dev));
+    TreeHandle* t = nullptr;
+    TRY(tree_new_like(*src, &t));
+    const int rc = copy_one(tree_copy_desc(*src, *t, nullptr, t->cap), ctx()->stream);
+    if (rc) {
+        tree_free(t);
+        return rc;
+    }
+    t->count = src->count;
+    *out = t;
+    return MK_OK;
+}
+
+int tree_copy(TreeHandle* dst, TreeHandle* src) {
+    if (!dst || !src) return fail(MK_EINVAL, "null pointer");
+    if (dst == src) return MK_OK;
+    // Both handles' mutexes, always the one at the lower address first: two
+    // threads copying a <- b and b <- a take them in the same order.
+    std::mutex *first = &dst->mu, *second = &src->mu;
+    if (std::less<std::mutex*>()(second, first)) std::swap(first, second);
+    std::lock_guard<std::mutex> l1(*first);
+    std::lock_guard<std::mutex> l2(*second);
+    if (!tree_same_shape(*dst, *src))
+        return fail(MK_EINVAL, "a copy between a %s of %u-byte %s and a %s of %u-byte %s, or of another layout",
+                    dst->kind->name, dst->item_len, dst->kind->noun, src->kind->name, src->item_len, src->kind->noun);
+    if (dst->dev != src->dev) return fail(MK_EINVAL, "the trees live on devices %d and %d", dst->dev, src->dev);
+    TRY(bind_dev(src->dev));
+    const bool regrow = src->count > dst->cap;  // else dst keeps its capacity
+    TreeBufs nb;
+    if (regrow) TRY(tree_bufs_alloc(*src, src->cap, false, nb));  // before anything is enqueued: a failure leaves dst as it was
+    const uint64_t cap = regrow ? src->cap : dst->cap;
+    const int rc = copy_one(tree_copy_desc(*src, *dst, regrow ? &nb : nullptr, cap), ctx()->stream);
+    if (rc) {
+        tree_bufs_free(nb);
+        return rc;
+    }
+    if (regrow) tree_bufs_install(dst, nb, cap);
+    dst->count = src->count;
+    return MK_OK;
+}
+
+int tree_reserve(TreeHandle* t, uint64_t capacity) {
+    if (!t) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    if (capacity <= t->cap) return MK_OK;
+    TRY(t->kind->check_shape(t->count, capacity, t->item_len));
+    TRY(bind_dev(t->dev));
+    TreeBufs nb;  // a root of its own: no destination range of the copy may be one of its sources
+    TRY(tree_bufs_alloc(*t, capacity, true, nb));
+    const int rc = copy_one(tree_copy_desc(*t, *t, &nb, capacity), ctx()->stream);
+    if (rc) {
+        tree_bufs_free(nb);
+        return rc;
+    }
+    tree_bufs_install(t, nb, capacity);
     return MK_OK;
 }
 

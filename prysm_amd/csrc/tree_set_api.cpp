@@ -4,6 +4,8 @@
 // them.  Changes are collected on the host (tree_set_plan.cpp); a root is one
 // upload, the update over all the trees (tree_many_api.cpp) and one 32-B
 // read-back.
+#include <functional>
+
 #include "runtime.hpp"
 #include "tree_set_plan.hpp"
 
@@ -344,9 +346,171 @@ int set_branches(mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k,
     return MK_OK;
 }
 
+// ---- clone, copy, reserve ---------------------------------------------------------
+// everything pending onto the device and waited for: the handles hold what root() would describe
+int settle(mk_tree_set* s) {
+    if (!s->dirty || s->trees.empty()) return MK_OK;
+    TRY(bind_set(s));
+    TRY(flush(s));
+    HIPCHK(hipStreamSynchronize(ctx()->stream));
+    flushed(s);
+    return MK_OK;
+}
+
+bool same_fields(const std::vector<mk_field>& a, const std::vector<mk_field>& b) {
+    return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(mk_field)));
+}
+
+// src (settled) into dst, whose trees are handles of src's shapes, tree by
+// tree: every buffer a too-small destination tree needs first, then ONE copy
+// launch over all the trees and the container root, the message as the device
+// holds it (what mk_tree_set_branches hands out) behind it on the stream, one
+// synchronise; then the host side.  Both sets locked, their device bound.
+int copy_trees(mk_tree_set* dst, mk_tree_set* src) {
+    const uint32_t nt = (uint32_t)src->trees.size();
+    if (nt == 0) {
+        dst->msg = src->msg;
+        dst->dirty = false;
+        return MK_OK;
+    }
+    hipStream_t st = ctx()->stream;
+    std::vector<TreeBufs> nb(nt);
+    mk_tree_copy table[MK_TREES_MAX] = {};
+    const bool extra = src->container_len && nparts(src) && src->croot.p;
+    int rc = MK_OK;
+    for (uint32_t i = 0; i < nt && !rc; ++i) {  // a failed allocation leaves dst's trees as they were
+        const TreeHandle& sh = *src->trees[i].h;
+        const TreeHandle& dh = *dst->trees[i].h;
+        const bool regrow = sh.count > dh.cap;
+        if (regrow) rc = tree_bufs_alloc(sh, sh.cap, false, nb[i]);
+        if (!rc) table[i] = tree_copy_desc(sh, dh, regrow ? &nb[i] : nullptr, regrow ? sh.cap : dh.cap);
+    }
+    if (!rc && extra) rc = grow(dst->croot, 32);
+    if (!rc && extra) rc = grow(dst->stage, src->stage.cap);
+    if (!rc) rc = trees_copy_check(table, nt, extra ? src->croot.p : nullptr, extra ? dst->croot.p : nullptr);
+    if (!rc) rc = trees_copy_launch(table, nt, extra ? src->croot.p : nullptr, extra ? dst->croot.p : nullptr, st);
+    if (!rc && extra &&
+        hipMemcpyAsync(dst->stage.p, src->stage.p, src->container_len, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        rc = fail(MK_EHIP, "hipMemcpyAsync failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(MK_EHIP, "hipStreamSynchronize failed");
+    if (rc) {
+        for (TreeBufs& b : nb) tree_bufs_free(b);
+        dst->dirty = true;  // its message in HBM may be gone: the next flush writes it again
+        return rc;
+    }
+    for (uint32_t i = 0; i < nt; ++i) {
+        TreeHandle* dh = dst->trees[i].h;
+        if (nb[i].items.p) tree_bufs_install(dh, nb[i], src->trees[i].h->cap);
+        dh->count = src->trees[i].h->count;
+        sp::record_assign(dst->pend[i], dh->count, dh->cap);  // its pending changes are dropped
+    }
+    dst->msg = src->msg;
+    dst->dirty = false;
+    return MK_OK;
+}
+
+// the two sets' mutexes, always the one at the lower address first (as tree_copy takes two handles')
+struct LockBoth {
+    std::mutex *a, *b;
+    LockBoth(std::mutex& x, std::mutex& y) : a(&x), b(&y) {
+        if (std::less<std::mutex*>()(b, a)) std::swap(a, b);
+        a->lock();
+        b->lock();
+    }
+    ~LockBoth() {
+        b->unlock();
+        a->unlock();
+    }
+};
+
+int set_clone(mk_tree_set* src, mk_tree_set** out) {
+    if (!src || !out) return fail(MK_EINVAL, "null pointer");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(src->mu);
+    TRY(settle(src));
+    if (!src->trees.empty()) TRY(bind_set(src));
+    auto* s = new (std::nothrow) mk_tree_set();
+    if (!s) return fail(MK_ENOMEM, "tree set allocation failed");
+    s->dev = src->dev;
+    s->container_len = src->container_len;
+    int rc = MK_OK;
+    for (size_t i = 0; i < src->trees.size() && !rc; ++i) {
+        const mk_tree_set::Tree& t = src->trees[i];
+        mk_tree_set::Tree c;
+        rc = tree_new_like(*t.h, &c.h);
+        if (rc) break;
+        c.kind = t.kind;
+        c.coff = t.coff;
+        c.fields = t.fields;
+        sp::Pending p;
+        p.item_len = t.h->item_len;
+        p.rebuild_div = t.h->kind->rebuild_div;
+        p.cap = c.h->cap;
+        s->trees.push_back(std::move(c));
+        s->pend.push_back(std::move(p));
+    }
+    if (!rc) rc = copy_trees(s, src);
+    if (rc) {
+        mk_tree_set_free(s);
+        return rc;
+    }
+    *out = s;
+    return MK_OK;
+}
+
+int set_copy(mk_tree_set* dst, mk_tree_set* src) {
+    if (!dst || !src) return fail(MK_EINVAL, "null pointer");
+    if (dst == src) return MK_OK;
+    LockBoth lk(dst->mu, src->mu);
+    if (dst->container_len != src->container_len)
+        return fail(MK_EINVAL, "containers of %u and %u bytes", dst->container_len, src->container_len);
+    if (dst->trees.size() != src->trees.size())
+        return fail(MK_EINVAL, "sets of %zu and %zu trees", dst->trees.size(), src->trees.size());
+    for (size_t i = 0; i < src->trees.size(); ++i) {
+        const mk_tree_set::Tree &d = dst->trees[i], &t = src->trees[i];
+        if (d.kind != t.kind || d.h->item_len != t.h->item_len || d.coff != t.coff || !same_fields(d.fields, t.fields))
+            return fail(MK_EINVAL, "tree %zu differs in kind, item length, record layout or container offset", i);
+    }
+    if (!src->trees.empty() && dst->dev != src->dev)
+        return fail(MK_EINVAL, "the sets live on devices %d and %d", dst->dev, src->dev);
+    TRY(settle(src));
+    if (!src->trees.empty()) TRY(bind_set(src));
+    return copy_trees(dst, src);
+}
+
+int set_reserve(mk_tree_set* s, uint32_t tree, uint64_t capacity) {
+    if (!s) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    TRY(tree_reserve(s->trees[tree].h, capacity));  // what is pending stays pending
+    s->pend[tree].cap = s->trees[tree].h->cap;
+    return MK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mk_tree_set_clone(mk_call* call, mk_tree_set* src, mk_tree_set** out) {
+    Scope S(call);
+    return S.done(set_clone(src, out));
+}
+
+int mk_tree_set_copy(mk_call* call, mk_tree_set* dst, mk_tree_set* src) {
+    Scope S(call);
+    return S.done(set_copy(dst, src));
+}
+
+int mk_tree_set_reserve(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t capacity) {
+    Scope S(call);
+    return S.done(set_reserve(s, tree, capacity));
+}
+
+uint64_t mk_tree_set_capacity(const mk_tree_set* s, uint32_t tree) {
+    if (!s) return 0;
+    std::lock_guard<std::mutex> lk(const_cast<mk_tree_set*>(s)->mu);
+    return tree < s->trees.size() ? s->trees[tree].h->cap : 0;
+}
 
 // No device is needed before the first tree is added: a bad argument is MK_EINVAL on any machine.
 int mk_tree_set_new(mk_call* call, uint32_t container_len, mk_tree_set** out) {

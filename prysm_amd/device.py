@@ -887,6 +887,57 @@ def trees_update(trees, container: torch.Tensor = None, container_len: int = 0,
                 device=dev)
 
 
+class TreeCopyArgs:
+    """One tree of ``trees_copy`` (mk_tree_copy): the ``n`` values of a built
+    tree of ``kind`` laid out for ``src_capacity`` values in ``src_*`` go into
+    the layout of ``dst_capacity`` values in ``dst_*``.  ``*_level0``: the struct
+    roots / element digests of a STRUCT / BYTES tree (None for a list tree)."""
+
+    def __init__(self, kind: int, item_len: int, n: int, src_capacity: int, dst_capacity: int,
+                 src_items: torch.Tensor, src_levels: torch.Tensor, src_root: torch.Tensor,
+                 dst_items: torch.Tensor, dst_levels: torch.Tensor, dst_root: torch.Tensor,
+                 src_level0: torch.Tensor = None, dst_level0: torch.Tensor = None):
+        self.kind, self.item_len, self.n = kind, item_len, n
+        self.src_capacity, self.dst_capacity = src_capacity, dst_capacity
+        self.src = (src_items, src_level0, src_levels, src_root)
+        self.dst = (dst_items, dst_level0, dst_levels, dst_root)
+
+
+def trees_copy(trees, extra_src: torch.Tensor = None, extra_dst: torch.Tensor = None) -> None:
+    """Copy up to 16 built resident trees (``TreeCopyArgs``) between the
+    layouts of two capacities, and optionally 32 more bytes (``extra_src`` ->
+    ``extra_dst``: a container root), in one launch on the current stream
+    (mk_dev_ssz_trees_copy).  Nothing is hashed, uploaded or
+    allocated: the call can be captured.  Only the live part of each tree is
+    read and written; the rest of the destination buffers stays as it was."""
+    arr = (_lib.TreeCopy * max(len(trees), 1))()
+    for a, t in zip(arr, trees):
+        leaf = t.item_len if t.kind == _lib.MK_TREE_LIST else 32
+        for side, cap in ((t.src, t.src_capacity), (t.dst, t.dst_capacity)):
+            items, level0, levels, root = side
+            if items is not None and items.numel() * items.element_size() < t.n * t.item_len:
+                raise ValueError("value buffer shorter than n * item_len")
+            if level0 is not None and level0.numel() * level0.element_size() < 32 * t.n:
+                raise ValueError("level-0 buffer shorter than 32 * n")
+            if levels is not None and levels.numel() * levels.element_size() < list_tree_levels_bytes(cap, leaf):
+                raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, leaf length)")
+            if root is not None and root.numel() * root.element_size() < 32:
+                raise ValueError("root buffer shorter than 32 bytes")
+        a.kind, a.item_len, a.n = t.kind, t.item_len, t.n
+        a.src_capacity, a.dst_capacity = t.src_capacity, t.dst_capacity
+        for name, x in zip(("items", "level0", "levels", "root32"), t.src):
+            setattr(a, f"d_src_{name}", x.data_ptr() if x is not None else None)
+        for name, x in zip(("items", "level0", "levels", "root32"), t.dst):
+            setattr(a, f"d_dst_{name}", x.data_ptr() if x is not None else None)
+    if (extra_src is None) != (extra_dst is None):
+        raise ValueError("the 32-byte extra needs a source and a destination")
+    some = next((x for t in trees for x in t.dst + t.src if x is not None), extra_dst)
+    if some is None:
+        return  # no tree and no extra: nothing to do
+    _lib.invoke("mk_dev_ssz_trees_copy", arr, len(trees), _p(extra_src) if extra_src is not None else None,
+                _p(extra_dst) if extra_dst is not None else None, _stream(some.device), device=_dev(some))
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

@@ -149,6 +149,37 @@ class _Tree:
         self._call("branches", _ptr(idx), idx.size, _ptr(values), _ptr(out))
         return values, out
 
+    # ---- a second resident tree, or more room, without uploading or hashing anything
+    @property
+    def capacity(self) -> int:
+        """Values the tree has room for before an append rebuilds it."""
+        return int(getattr(_lib.load(), f"mk_{self._prefix}_capacity")(self._handle))
+
+    def clone(self):
+        """A new tree of the same kind, value length, layout and capacity
+        holding this list: one copy launch in HBM.  The two share nothing
+        afterwards (a candidate block's post-state, the other side of a fork)."""
+        h = ctypes.c_void_p()
+        self._call("clone", ctypes.byref(h))
+        t = object.__new__(type(self))
+        t.__dict__.update(self.__dict__)
+        t._handle = h
+        return t
+
+    def copy_from(self, other) -> None:
+        """Make this tree a copy of ``other`` (the same kind, value length and
+        layout, else it raises and nothing changes).  It keeps its capacity
+        when ``other``'s values fit and takes ``other``'s otherwise."""
+        if type(other) is not type(self):
+            raise _lib.MerkleError(_lib.MK_EINVAL, f"copy_from: a {type(other).__name__} into a {type(self).__name__}")
+        self._call("copy", other._handle)
+
+    def reserve(self, capacity: int) -> None:
+        """Room for ``capacity`` values: the tree moves into the layout of the
+        new capacity on the device; root, count and values stay.  A smaller
+        ``capacity`` than the current one does nothing."""
+        self._call("reserve", int(capacity))
+
 
 def verify_branches(values, indices, n: int, item_len: int, branches, root, container=None,
                     container_off: int = None, device: int = -1) -> np.ndarray:
@@ -363,6 +394,35 @@ class TreeSet:
         out = np.empty((max(count, 0), self._len[tree]), dtype=np.uint8)
         self._call("items", tree, first, count, _ptr(out))
         return out
+
+    # ---- a second resident state, or more room for one tree
+    def capacity(self, tree) -> int:
+        """Values a tree has room for before a flush has to rebuild it."""
+        return int(_lib.load().mk_tree_set_capacity(self._handle, self._tree(tree)))
+
+    def clone(self):
+        """A new set of the same trees holding this one's lists and message,
+        pending changes included (they are flushed first, as ``root()`` does):
+        one copy launch over all the trees and the container root, nothing
+        uploaded, nothing hashed.  The two share nothing afterwards; a subclass
+        keeps its type and whatever it knows its trees by."""
+        h = ctypes.c_void_p()
+        self._call("clone", ctypes.byref(h))
+        s = object.__new__(type(self))
+        s.__dict__.update({k: (v.copy() if isinstance(v, (list, dict)) else v) for k, v in self.__dict__.items()})
+        s._handle = h
+        return s
+
+    def copy_from(self, other) -> None:
+        """Make this set a copy of ``other`` (flushed first), dropping what
+        this one has pending: the way back after a block that failed.  The sets
+        must agree in container length and, tree by tree, in kind, value length,
+        layout and container offset, else it raises and nothing changes."""
+        self._call("copy", other._handle)
+
+    def reserve(self, tree, capacity: int) -> None:
+        """Room for ``capacity`` values in one tree; pending changes stay pending."""
+        self._call("reserve", self._tree(tree), int(capacity))
 
     def leaf_len(self, tree) -> int:
         """Bytes of a level-0 entry of a tree: what ``branches`` proves."""

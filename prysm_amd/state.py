@@ -749,6 +749,12 @@ class BeaconTreeSet(TreeSet):
         msg = b"".join(_st.pack("<Q", int(x)) for x in fork)
         self.put(CONTAINER_OFF["Fork"], hash_batch_var([msg])[0])
 
+    def clone(self) -> "BeaconTreeSet":
+        """A second resident state (``TreeSet.clone``) that knows
+        its trees by the same names: run a block's transition on it, compare
+        ``root()`` with the block's state root, keep it or drop it."""
+        return super().clone()
+
     def assign_state(self, state: BeaconState) -> None:
         """Every small field put, every list assigned from ``state``."""
         for name in _SCALARS:
