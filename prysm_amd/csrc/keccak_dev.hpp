@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "keccak_sparse.hpp"  // round 0 of a mostly-zero state
 #include "plan_types.hpp"  // MK_LOCK_BARS
 
 namespace mk {
@@ -206,6 +207,52 @@ __device__ __forceinline__ void round_asm(State& s, uint32_t rclo, uint32_t rchi
 
 __device__ __forceinline__ void round_fn(State& s, uint32_t rclo, uint32_t rchi) { round_asm(s, rclo, rchi); }
 
+// The instructions of the sparse round 0 (keccak_sparse.hpp) in round_asm's
+// form: one asm volatile statement each, the locked round's barriers at the
+// same two positions (every wave of a locked workgroup runs the same number
+// of s_barriers whichever form its round 0 takes).
+__device__ __forceinline__ uint32_t ax2(uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm volatile("v_xor_b32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t ax3s(uint32_t a, uint32_t b, uint32_t s) {
+    uint32_t r;
+    asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "s"(s));
+    return r;
+}
+template <bool BAR>
+struct AsmOps {
+    static __device__ __forceinline__ uint32_t x2(uint32_t a, uint32_t b) { return ax2(a, b); }
+    static __device__ __forceinline__ uint32_t x3(uint32_t a, uint32_t b, uint32_t c) { return ax3(a, b, c); }
+    static __device__ __forceinline__ uint32_t xk(uint32_t a, uint32_t k) { return axs(a, k); }
+    static __device__ __forceinline__ uint32_t x3k(uint32_t a, uint32_t b, uint32_t k) { return ax3s(a, b, k); }
+    static __device__ __forceinline__ uint32_t chi(uint32_t a, uint32_t b, uint32_t c) { return achi(a, b, c); }
+    template <int N>
+    static __device__ __forceinline__ void rot(uint32_t lo, uint32_t hi, uint32_t& olo, uint32_t& ohi) {
+        arot<N>(lo, hi, olo, ohi);
+    }
+    static __device__ __forceinline__ void bar_theta() {
+        if constexpr (BAR && MK_LOCK_BARS >= 2) __builtin_amdgcn_s_barrier();
+    }
+    static __device__ __forceinline__ void bar_chi() {
+        if constexpr (BAR) __builtin_amdgcn_s_barrier();
+    }
+};
+// What a permutation starts from (its round 0): any state, a 64-B node
+// message (lanes 0..7 set, the pad lanes 8 and 16 implied), or a message's
+// first block (lanes 0..16 set).  The sparse forms read only the set lanes.
+enum Start { kAnyState = 0, kNodeMsg = 1, kBlock17 = 2 };
+template <Start ST, bool BAR>
+__device__ __forceinline__ void round0(State& s) {
+    if constexpr (ST == kNodeMsg)
+        sparse::round0_node<AsmOps<BAR>>(s, kRcLo[0], kRcHi[0]);
+    else if constexpr (ST == kBlock17)
+        sparse::round0_block17<AsmOps<BAR>>(s, kRcLo[0], kRcHi[0]);
+    else
+        round_asm<BAR>(s, kRcLo[0], kRcHi[0]);
+}
+
 #ifndef MK_ROUND_UNROLL
 #define MK_ROUND_UNROLL 2
 #endif
@@ -293,11 +340,12 @@ __device__ __forceinline__ void keccak_f_lock_mid(State& s, F&& mid) {
 }
 // Locked permutation with `m1` run after round K1 and `m2` after round K2
 // (0 < K1 < K2 < 24).
-template <int K1, int K2, typename F1, typename F2>
+template <int K1, int K2, Start ST = kAnyState, typename F1, typename F2>
 __device__ __forceinline__ void keccak_f_lock_mid2(State& s, F1&& m1, F2&& m2) {
     static_assert(K1 > 0 && K1 < K2 && K2 < 24, "mid points");
+    if constexpr (ST != kAnyState) round0<ST, true>(s);
 #pragma unroll kRoundUnroll
-    for (int r = 0; r < K1; ++r) round_asm<true>(s, kRcLo[r], kRcHi[r]);
+    for (int r = ST != kAnyState ? 1 : 0; r < K1; ++r) round_asm<true>(s, kRcLo[r], kRcHi[r]);
     m1();
 #pragma unroll kRoundUnroll
     for (int r = K1; r < K2; ++r) round_asm<true>(s, kRcLo[r], kRcHi[r]);
@@ -357,10 +405,19 @@ __device__ __forceinline__ void keccak_f_digest_lock_mid3(State& s, F1&& m1, F2&
     asm volatile("" : "+v"(s.lo[0]), "+v"(s.hi[0]), "+v"(s.lo[1]), "+v"(s.hi[1]), "+v"(s.lo[2]), "+v"(s.hi[2]),
                  "+v"(s.lo[3]), "+v"(s.hi[3]));
 }
+// ST = kNodeMsg: the sparse round 0, then rounds 1..22 in the unrolled loop
+// (an even count: no straight-line round 22)
+template <Start ST = kAnyState>
 __device__ __forceinline__ void keccak_f_digest_lock(State& s) {
+    if constexpr (ST != kAnyState) {
+        round0<ST, true>(s);
 #pragma unroll kRoundUnroll
-    for (int r = 0; r < 22; ++r) round_asm<true>(s, kRcLo[r], kRcHi[r]);
-    round_asm<true>(s, kRcLo[22], kRcHi[22]);
+        for (int r = 1; r < 23; ++r) round_asm<true>(s, kRcLo[r], kRcHi[r]);
+    } else {
+#pragma unroll kRoundUnroll
+        for (int r = 0; r < 22; ++r) round_asm<true>(s, kRcLo[r], kRcHi[r]);
+        round_asm<true>(s, kRcLo[22], kRcHi[22]);
+    }
     last_round_digest(s, kRcLo[23], kRcHi[23]);
     asm volatile("" : "+v"(s.lo[0]), "+v"(s.hi[0]), "+v"(s.lo[1]), "+v"(s.hi[1]), "+v"(s.lo[2]), "+v"(s.hi[2]),
                  "+v"(s.lo[3]), "+v"(s.hi[3]));

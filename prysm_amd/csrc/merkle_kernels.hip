@@ -232,11 +232,9 @@ __device__ __forceinline__ void hash_node_lock(uint4 l0, uint4 l1, uint4 r0, uin
     s.lo[2] = l1.x; s.hi[2] = l1.y; s.lo[3] = l1.z; s.hi[3] = l1.w;
     s.lo[4] = r0.x; s.hi[4] = r0.y; s.lo[5] = r0.z; s.hi[5] = r0.w;
     s.lo[6] = r1.x; s.hi[6] = r1.y; s.lo[7] = r1.z; s.hi[7] = r1.w;
-#pragma unroll
-    for (int k = 8; k < 25; ++k) s.lo[k] = s.hi[k] = 0;
-    s.lo[8] = 1u;  // byte 64
-    s.hi[16] = 0x80000000u;
-    keccak_f_digest_lock(s);
+    // the pad (0x01 at byte 64, 0x80 at byte 135) and the zero lanes are
+    // implied by the sparse round 0, which reads lanes 0..7 only
+    keccak_f_digest_lock<kNodeMsg>(s);
     digest(s, d0, d1);
 }
 
@@ -482,42 +480,116 @@ k_reduce(ReduceArgs a) {
 constexpr int kLockAux = 2;  // global_load_lds aux: nt
 // the side configs' locked kernels (C2 messages, C3 records): inputs read once, default policy (nt not kept)
 constexpr int kSideAux = 0;
+//
+// Staging addresses.  Instruction i of a phase moves flat units U = 64 i +
+// lane, unit u = U mod NU of window m = U / NU (NU = 9 or 7), from byte
+// 1024 m + 16 u of the wave's region.  Both NU divide 63, so from one
+// instruction to the next (m, u) -> (m + 63 / NU, u + 1) with one wrap, and
+// instruction i is the lane's own (m0, u0) of instruction 0 plus a constant,
+// plus 1024 - 16 NU on the lanes that have wrapped by then.  Which lanes
+// those are is a compile-time lane set (lane mod NU >= NU - i): an SGPR-pair
+// constant selects on it, so there is no division (v_mul_hi_u32, shifts, a
+// multiply back) and no compare.  The lane's two byte offsets at instruction
+// 0 (phase A in the low half, phase B in the high half) are one VGPR for the
+// whole kernel (lock_dma_seed), laundered at every call so that nothing
+// larger is hoisted; the constant goes into the wave-uniform base, and the
+// instruction takes that base in SGPRs with the 32-bit lane offset (no
+// 64-bit per-lane add).  Per DMA instruction 2 VALU (phase B) or 3 (phase A,
+// whose position 8 repeats unit 7), all full rate, against 11 with a
+// quarter-rate v_mul_hi_u32 and four 64-bit adds before
+// (profiles/r07/leaf_nonround_valu.md).
+__device__ __forceinline__ uint32_t lock_dma_seed(uint32_t lane) {
+    const uint32_t m9 = lane / 9, u9 = lane - 9 * m9, m7 = lane / 7, u7 = lane - 7 * m7;
+    return (1024 * m9 + 16 * u9) | (1024 * m7 + 16 * u7) << 16;
+}
+// lanes whose unit has wrapped into the next window by instruction i / sits at position NU - 1 there
+template <int NU>
+constexpr uint64_t lock_lanes_wrapped(int i) {
+    uint64_t s = 0;
+    for (int l = 0; l < 64; ++l) s |= (uint64_t)(l % NU + i >= NU) << l;
+    return s;
+}
+template <int NU>
+constexpr uint64_t lock_lanes_last(int i) {
+    uint64_t s = 0;
+    for (int l = 0; l < 64; ++l) s |= (uint64_t)((l + 64 * i) % NU == NU - 1) << l;
+    return s;
+}
+// lanes of the set ? b : 0
+__device__ __forceinline__ uint32_t lock_sel0(uint32_t b, uint64_t lanes) {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(b), "s"(lanes));
+    return r;
+}
+// lanes of the set ? b : A (A, an inline constant)
+template <int A>
+__device__ __forceinline__ uint32_t lock_sel_else(uint32_t b, uint64_t lanes) {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "n"(A), "v"(b), "s"(lanes));
+    return r;
+}
+// lanes of the set ? 0 : a
+__device__ __forceinline__ uint32_t lock_clear(uint32_t a, uint64_t lanes) {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, %1, 0, %2" : "=v"(r) : "v"(a), "s"(lanes));
+    return r;
+}
+// lanes of the set ? 0 : A
+template <int A>
+__device__ __forceinline__ uint32_t lock_clear_imm(uint64_t lanes) {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, %1, 0, %2" : "=v"(r) : "n"(A), "s"(lanes));
+    return r;
+}
+// 16 B per lane from `base` (wave-uniform, kept in SGPRs) + off into row..row + 63 of the wave's image
+template <int AUX>
+__device__ __forceinline__ void lock_dma_issue(uint4* row, const uint4* base, uint32_t off) {
+    asm("" : "+s"(base));  // the constant part stays in the scalar base
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(reinterpret_cast<const char*>(base) + off),
+                                     (__attribute__((address_space(3))) void*)row, 16, 0, AUX);
+}
+// instructions [I0, I1) of the NU (a part of a split issue); Rj, Bw wave-uniform
 template <int NU, int U0, int AUX = 0, int I0 = 0, int I1 = NU>
-__device__ __forceinline__ void lock_dma_c(uint4* Bw, const uint4* __restrict__ Rj, uint32_t lane) {
-    // launder the lane index so the per-lane offsets are recomputed here (a
-    // few VALU per DMA) instead of being hoisted and held in 16+ VGPRs;
-    // instructions [I0, I1) of the NU (a part of a split issue)
-    asm volatile("" : "+v"(lane));
+__device__ __forceinline__ void lock_dma_c(uint4* Bw, const uint4* __restrict__ Rj, uint32_t seed) {
+    static_assert(NU == 7 && 63 % NU == 0, "the seed's high half is the stride-7 image");
+    asm volatile("" : "+v"(seed));
+    const uint32_t off0 = seed >> 16;
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
-        const uint32_t U = 64u * i + lane;
-        const uint32_t m = U / NU, u = U - m * NU;
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + m * 64 + U0 + u),
-                                         (__attribute__((address_space(3))) void*)(Bw + 64 * i), 16, 0, AUX);
+        const uint32_t off = i ? off0 + lock_sel0(1024u - 16u * NU, lock_lanes_wrapped<NU>(i)) : off0;
+        lock_dma_issue<AUX>(Bw + 64 * i, Rj + (63 / NU) * 64 * i + i + U0, off);
     }
 }
 // phase A of a window step (block 1 = units 0..8); instructions [I0, I1) of
 // the 9 (+ the unit-8 copy with the last part)
 template <int I0 = 0, int I1 = 9>
-__device__ __forceinline__ void lock_dma_a(uint4* Bw, const uint4* __restrict__ Rj, uint32_t lane) {
-    asm volatile("" : "+v"(lane));
+__device__ __forceinline__ void lock_dma_a(uint4* Bw, const uint4* __restrict__ Rj, uint32_t seed, uint32_t lane) {
+    asm volatile("" : "+v"(seed));
+    const uint32_t off0 = seed & 0xFFFFu;
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
-        const uint32_t U = 64u * i + lane;
-        const uint32_t m = U / 9, u = U - m * 9;
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + m * 64 + (u < 8 ? u : 7)),
-                                         (__attribute__((address_space(3))) void*)(Bw + 64 * i), 16, 0, kLockAux);
+        // position 8 repeats unit 7: those lanes step back one unit.  The
+        // lane offset is unsigned (lane 0 at i = 8 would go below zero), so
+        // the base is one unit low and every other lane adds the unit back:
+        // at i = 0 the base is Rj - 1, which for the first wave of the first
+        // group lies 16 B below the items, but no lane reads below Rj -- a
+        // lane adds 16, or is at position 8 with off0 >= 128.
+        const uint32_t d = i ? lock_clear(lock_sel_else<16>(1024u - 16u * 9 + 16u, lock_lanes_wrapped<9>(i)),
+                                          lock_lanes_last<9>(i))
+                             : lock_clear_imm<16>(lock_lanes_last<9>(i));
+        lock_dma_issue<kLockAux>(Bw + 64 * i, Rj + 7 * 64 * i + i - 1, off0 + d);
     }
-    if constexpr (I1 == 9)
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(Rj + lane * 64 + 8),
-                                         (__attribute__((address_space(3))) void*)(Bw + 576), 16, 0, 0);
+    if constexpr (I1 == 9) {
+        asm volatile("" : "+v"(lane));  // lane << 10 recomputed here as a 32-bit offset, not held as a 64-bit pair
+        lock_dma_issue<0>(Bw + 576, Rj + 8, lane << 10);
+    }
 }
 
 // `after_wait` runs right after phase A's wait: the previous group's output
 // store goes there, so no wait ever covers a store issued just before it
 // (stores count in vmcnt; a store's wait is the write's round trip).
 template <typename F>
-__device__ __forceinline__ void hash_window_sc(uint4* Bw, uint32_t lane, const uint4* __restrict__ Rj,
+__device__ __forceinline__ void hash_window_sc(uint4* Bw, uint32_t lane, uint32_t seed, const uint4* __restrict__ Rj,
                                                const uint4* __restrict__ Rnext, uint4& d0, uint4& d1,
                                                F&& after_wait) {
     State s;
@@ -534,13 +606,12 @@ __device__ __forceinline__ void hash_window_sc(uint4* Bw, uint32_t lane, const u
     const uint4 v8 = Bw[576 + lane];
     s.lo[16] = v8.x;
     s.hi[16] = v8.y;
-#pragma unroll
-    for (int k = 17; k < 25; ++k) s.lo[k] = s.hi[k] = 0;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // rows read: phase B may overwrite them
-    lock_dma_c<7, 9, kLockAux, 0, 3>(Bw, Rj, lane);  // phase B in three parts over the first permutation
-    keccak_f_lock_mid2<MK_LOCK_SPLIT_B1, MK_LOCK_SPLIT_B2>(
-        s, [&] { lock_dma_c<7, 9, kLockAux, 3, 5>(Bw, Rj, lane); },
-        [&] { lock_dma_c<7, 9, kLockAux, 5, 7>(Bw, Rj, lane); });
+    lock_dma_c<7, 9, kLockAux, 0, 3>(Bw, Rj, seed);  // phase B in three parts over the first permutation
+    // lanes 17..24 start at zero: the sparse round 0 reads lanes 0..16 only
+    keccak_f_lock_mid2<MK_LOCK_SPLIT_B1, MK_LOCK_SPLIT_B2, kBlock17>(
+        s, [&] { lock_dma_c<7, 9, kLockAux, 3, 5>(Bw, Rj, seed); },
+        [&] { lock_dma_c<7, 9, kLockAux, 5, 7>(Bw, Rj, seed); });
     s.lo[0] ^= v8.z;
     s.hi[0] ^= v8.w;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // phase B has landed
@@ -559,9 +630,9 @@ __device__ __forceinline__ void hash_window_sc(uint4* Bw, uint32_t lane, const u
     // permutation: late enough that little of the data streamed in between
     // evicts the line block 2 shares with it, early enough to land in time
     keccak_f_digest_lock_mid3<MK_LOCK_SPLIT_A1, MK_LOCK_SPLIT_A2, MK_LOCK_DMA_ROUND>(  // in three parts
-        s, [&] { if (Rnext) lock_dma_a<0, 3>(Bw, Rnext, lane); },
-        [&] { if (Rnext) lock_dma_a<3, 6>(Bw, Rnext, lane); },
-        [&] { if (Rnext) lock_dma_a<6, 9>(Bw, Rnext, lane); });
+        s, [&] { if (Rnext) lock_dma_a<0, 3>(Bw, Rnext, seed, lane); },
+        [&] { if (Rnext) lock_dma_a<3, 6>(Bw, Rnext, seed, lane); },
+        [&] { if (Rnext) lock_dma_a<6, 9>(Bw, Rnext, seed, lane); });
     digest(s, d0, d1);
 }
 
@@ -575,14 +646,17 @@ __global__ __launch_bounds__(kLockThreads, 1) void k_leaf_lock_sc(ReduceArgs a, 
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_leaf_stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
     __shared__ uint4 buf[kLockThreads / 64][10 * 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    // the wave index through readfirstlane: the region bases and the LDS image are then scalar values
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t seed = lock_dma_seed(lane);
     uint4* Bw = buf[wave];
     const uint4* items = reinterpret_cast<const uint4*>(a.items);
     uint4* out = reinterpret_cast<uint4*>(a.out);
     // the wave's 64 nodes = 256 consecutive windows (64 KB); lane m's windows at m * 64 uint4
     auto region = [&](uint64_t g) { return items + (g * kLockThreads + 64 * wave) * 64; };
     uint64_t g = blockIdx.x;
-    if (g < ngroups) lock_dma_a(Bw, region(g), lane);
+    if (g < ngroups) lock_dma_a(Bw, region(g), seed, lane);
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;  // the previous group's node, stored one group late
     uint64_t qnode = 0;
     bool pend = false;
@@ -599,11 +673,11 @@ __global__ __launch_bounds__(kLockThreads, 1) void k_leaf_lock_sc(ReduceArgs a, 
         const uint64_t gn = g + gridDim.x;
         const uint4* Rn = gn < ngroups ? region(gn) : nullptr;
         uint4 l0, l1, r0, r1, p0, p1;
-        hash_window_sc(Bw, lane, R, R + 16, l0, l1, flush);
-        hash_window_sc(Bw, lane, R + 16, R + 32, r0, r1, none);
+        hash_window_sc(Bw, lane, seed, R, R + 16, l0, l1, flush);
+        hash_window_sc(Bw, lane, seed, R + 16, R + 32, r0, r1, none);
         hash_node_lock(l0, l1, r0, r1, p0, p1);
-        hash_window_sc(Bw, lane, R + 32, R + 48, l0, l1, none);
-        hash_window_sc(Bw, lane, R + 48, Rn, r0, r1, none);
+        hash_window_sc(Bw, lane, seed, R + 32, R + 48, l0, l1, none);
+        hash_window_sc(Bw, lane, seed, R + 48, Rn, r0, r1, none);
         hash_node_lock(l0, l1, r0, r1, l0, l1);
         hash_node_lock(p0, p1, l0, l1, q0, q1);
         qnode = g * kLockThreads + threadIdx.x;

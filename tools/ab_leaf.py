@@ -32,6 +32,11 @@ def main():
     ap.add_argument("--log2n", type=int, default=26)
     ap.add_argument("--item-len", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warm", type=int, default=1,
+                    help="merkleHash A/B: untimed interleaved rounds first (the clock settles over the first few)")
+    ap.add_argument("--trees", type=int, default=1,
+                    help="merkleHash A/B: trees per build and round, back to back; a round's figure is their mean "
+                         "(one tree's time moves 2-5 %% from launch to launch on a busy box)")
     ap.add_argument("--trie", action="store_true", help="A/B the depth-32 deposit trie over 2^log2n x 280-B deposits")
     ap.add_argument("--struct", action="store_true", help="A/B the typed registry root of 1,000,000 validators")
     ap.add_argument("--c2", action="store_true", help="A/B the batched Keccak of 2^log2n x 64-B messages")
@@ -69,15 +74,18 @@ def main():
     outs = {v: torch.empty(32, dtype=torch.uint8, device=dev) for v in a.variants}
     times = {v: [] for v in a.variants}
     leaf = {v: [] for v in a.variants}
-    for r in range(a.rounds + 1):
+    for r in range(a.rounds + a.warm):
         for v, L in libs.items():
             L.mk_prof_enable(1)
             L.mk_prof_read(None, None, None, None, None)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            rc = L.mk_dev_ssz_merkle_hash(None, ctypes.c_void_p(items.data_ptr()), n, il,
-                                          ctypes.c_void_p(outs[v].data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                          ws.numel(), st)
+            for _ in range(a.trees):
+                rc = L.mk_dev_ssz_merkle_hash(None, ctypes.c_void_p(items.data_ptr()), n, il,
+                                              ctypes.c_void_p(outs[v].data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                              ws.numel(), st)
+                if rc:
+                    break
             e1.record()
             torch.cuda.synchronize()
             assert rc == 0, (v, rc)
@@ -86,12 +94,15 @@ def main():
             perms = ctypes.c_double()
             L.mk_prof_read(None, ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(perms), None)
             L.mk_prof_enable(0)
-            if r:  # round 0 is warmup
-                times[v].append(e0.elapsed_time(e1))
-                leaf[v].append(ms.value)
+            if r >= a.warm:
+                times[v].append(e0.elapsed_time(e1) / a.trees)
+                leaf[v].append(ms.value / max(1, cnt.value) if a.trees > 1 else ms.value)
     # "nl_*" variants are compute-only probes (MK_NOLOAD): their roots differ
     roots = {v: bytes(o.cpu().numpy()).hex() for v, o in outs.items() if not v.startswith("nl_")}
     assert len(set(roots.values())) <= 1, roots
+    for r in range(a.rounds):  # every interleaved round, so a reader can pair the variants round by round
+        print(json.dumps({"round": r + 1, "trees": a.trees, "tree_ms": {v: round(times[v][r], 4) for v in a.variants},
+                          "leaf_ms": {v: round(leaf[v][r], 4) for v in a.variants}}))
     for v in a.variants:
         print(json.dumps({"variant": v, "log2n": a.log2n, "median_ms": statistics.median(times[v]),
                           "min_ms": min(times[v]), "leaf_median_ms": statistics.median(leaf[v]),
