@@ -896,6 +896,81 @@ int mk_tree_set_copy(mk_call* call, mk_tree_set* dst, mk_tree_set* src);
 int mk_tree_set_reserve(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t capacity);
 uint64_t mk_tree_set_capacity(const mk_tree_set* s, uint32_t tree);
 
+/* ---- resident trees audited on the device ------------------------- */
+/* Is a resident tree what its values say it is?  Every stored node is checked
+ * against what is stored below it, read-only and in HBM.  len0 = item_len for
+ * MK_TREE_LIST and 32 for MK_TREE_STRUCT / _BYTES; p, cb, nchunks, total and D
+ * as for mk_ssz_list_branch_bytes over len0.  The checks:
+ *   level 0 (STRUCT / BYTES), i < n: d_level0[32 i] against the struct hash of
+ *     record i / against K(le32(elem_len) || element i);
+ *   level 1, j < ceil(nchunks / 2): K(the level-0 bytes [2 j cb, min(total,
+ *     (2 j + 2) cb)), then 0^128 when 2 j + 1 == nchunks) against the stored node;
+ *   level d = 2 .. D, j < ceil(nchunks / 2^d): K(child 2j || child 2j+1), or
+ *     K(child 2j || 0^128) when 2j+1 is at or beyond level d - 1's count;
+ *   the root: K(top || le64(n) || 0^24) against d_root32, top node 0 of level D
+ *     or, for nchunks <= 1, the raw chunk (0^128 for n == 0);
+ *   the container (container_len > 0): K(message) against d_container_root32
+ *     (index 0) and, for each tree i with a container_off, the message's 32
+ *     bytes there against the tree's d_root32 (index 1 + i).
+ * Every count comes from n; the capacity only places the levels.  No node at or
+ * beyond a level's count and no level-0 byte at or beyond total is read.
+ * A mismatch has the key (level, index): level 0, 1 .. D, MK_AUDIT_ROOT for the
+ * root, MK_AUDIT_CONTAINER for the container checks.  A report holds the number
+ * of mismatches and the smallest key in (level, index) order; with none,
+ * first_level is MK_AUDIT_NONE and first_index is 2^64 - 1.  A wrong node is
+ * reported where it is stored and again one level up, where it is a child.
+ * mk_dev_ssz_trees_audit audits up to MK_TREES_MAX trees and the message: the
+ * reports are cleared on the stream, level 0 of the STRUCT / BYTES trees goes
+ * through the struct-roots / digest launches in pieces of at most 2^18 values
+ * into the workspace with a compare launch behind each, ONE launch checks every
+ * node of level >= 1, every root and the container, and a last one unpacks the
+ * keys.  d_reports: ntrees + 1 reports (8-B aligned), tree i's at i, the
+ * container's last (bad == 0 without a container).  Workspace (16-B aligned)
+ * from mk_ssz_trees_audit_workspace_bytes: it does not grow with n beyond the
+ * piece; 0 for list trees only (d_ws may then be NULL) and for a tree list the
+ * call would refuse.  d_level0 (NULL for MK_TREE_LIST), d_levels and d_root32
+ * 16-B aligned, records 4-B aligned, d_container and d_container_root32 4-B.
+ * MK_EINVAL, every check before a device is looked up and nothing launched:
+ * null or misaligned pointers where the shape needs them, an unknown kind,
+ * item_len == 0, a LIST item_len above 128, n > capacity, capacity * item_len
+ * overflowing, ntrees 0 or > MK_TREES_MAX, a level 0 or fields that do not match
+ * the kind, a bad field layout, container_len > MK_CONTAINER_MAX, a
+ * container_off that is misaligned, leaves the message, overlaps another or
+ * comes without a message, 2^31 or more work items; MK_ENOMEM: a short
+ * workspace.  Allocates nothing, uploads nothing, never synchronises, writes
+ * nothing but d_reports and d_ws, and can be captured into a hipGraph (a linear
+ * chain of nodes). */
+#define MK_AUDIT_ROOT 64u
+#define MK_AUDIT_CONTAINER 65u
+#define MK_AUDIT_NONE 0xffffffffu
+typedef struct mk_tree_audit {
+    uint32_t kind, item_len;       /* MK_TREE_LIST / _STRUCT / _BYTES; item / record / element length */
+    const void *d_items, *d_level0, *d_levels, *d_root32;
+    uint64_t n, capacity;
+    const mk_field* fields;        /* STRUCT only (host) */
+    uint32_t nfields;
+    uint32_t container_off;        /* byte offset of this tree's root in d_container, or MK_NO_CONTAINER */
+} mk_tree_audit;
+typedef struct mk_audit_report {
+    uint64_t bad;                  /* mismatches */
+    uint64_t first_index;          /* of the smallest key */
+    uint32_t first_level;          /* MK_AUDIT_NONE: no mismatch */
+    uint32_t pad;
+} mk_audit_report;
+uint64_t mk_ssz_trees_audit_workspace_bytes(const mk_tree_audit* trees, uint32_t ntrees);
+int mk_dev_ssz_trees_audit(mk_call* call, const mk_tree_audit* trees, uint32_t ntrees, const void* d_container,
+                           uint32_t container_len, const void* d_container_root32, void* d_reports, void* d_ws,
+                           uint64_t ws_bytes, void* stream);
+/* Handle forms: the audit of the handle's tree, one read-back of its report
+ * (*out).  mk_tree_set_audit flushes what is pending, as root does, then audits
+ * all the trees and the message in the same launch: out gets count + 1 reports,
+ * the container's last; a set without trees is MK_EINVAL.  The deposit trie has
+ * no audit. */
+int mk_list_tree_audit(mk_call* call, mk_list_tree* t, mk_audit_report* out);
+int mk_struct_list_tree_audit(mk_call* call, mk_struct_list_tree* t, mk_audit_report* out);
+int mk_bytes_list_tree_audit(mk_call* call, mk_bytes_list_tree* t, mk_audit_report* out);
+int mk_tree_set_audit(mk_call* call, mk_tree_set* s, mk_audit_report* out);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

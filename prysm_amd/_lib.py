@@ -213,6 +213,12 @@ _SIGS = {
     "mk_tree_set_copy": (_int, [_cp, _vp, _vp]),
     "mk_tree_set_reserve": (_int, [_cp, _vp, _u32, _u64]),
     "mk_tree_set_capacity": (_u64, [_vp, _u32]),
+    "mk_ssz_trees_audit_workspace_bytes": (_u64, [_vp, _u32]),
+    "mk_dev_ssz_trees_audit": (_int, [_cp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u64, _vp]),
+    "mk_list_tree_audit": (_int, [_cp, _vp, _vp]),
+    "mk_struct_list_tree_audit": (_int, [_cp, _vp, _vp]),
+    "mk_bytes_list_tree_audit": (_int, [_cp, _vp, _vp]),
+    "mk_tree_set_audit": (_int, [_cp, _vp, _vp]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),
@@ -255,6 +261,26 @@ class TreeCopy(ctypes.Structure):
     _fields_ = [("kind", _u32), ("item_len", _u32), ("n", _u64), ("src_capacity", _u64), ("dst_capacity", _u64),
                 ("d_src_items", _vp), ("d_src_level0", _vp), ("d_src_levels", _vp), ("d_src_root32", _vp),
                 ("d_dst_items", _vp), ("d_dst_level0", _vp), ("d_dst_levels", _vp), ("d_dst_root32", _vp)]
+
+
+MK_AUDIT_ROOT = 64            # a mismatch's level: the list root
+MK_AUDIT_CONTAINER = 65       # ... the container checks (the extra report)
+MK_AUDIT_NONE = 0xFFFFFFFF    # no mismatch
+
+
+class TreeAudit(ctypes.Structure):
+    """mk_tree_audit: one tree of mk_dev_ssz_trees_audit."""
+    _fields_ = [("kind", _u32), ("item_len", _u32), ("d_items", _vp), ("d_level0", _vp), ("d_levels", _vp),
+                ("d_root32", _vp), ("n", _u64), ("capacity", _u64), ("fields", _vp), ("nfields", _u32),
+                ("container_off", _u32)]
+
+
+class AuditReport(ctypes.Structure):
+    """mk_audit_report: mismatches and the smallest (level, index) among them."""
+    _fields_ = [("bad", _u64), ("first_index", _u64), ("first_level", _u32), ("pad", _u32)]
+
+    def astuple(self):
+        return int(self.bad), int(self.first_level), int(self.first_index)
 
 
 _lib = None

@@ -268,4 +268,9 @@ int mk_bytes_list_tree_reserve(mk_call* call, mk_bytes_list_tree* t, uint64_t ca
 
 uint64_t mk_bytes_list_tree_capacity(const mk_bytes_list_tree* t) { return t ? t->cap : 0; }
 
+int mk_bytes_list_tree_audit(mk_call* call, mk_bytes_list_tree* t, mk_audit_report* out) {
+    Scope S(call);
+    return S.done(tree_audit(t, out));
+}
+
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include "keccak_dev.hpp"
 #include "list_branch.hpp"
 #include "merkle_kernels.hpp"
+#include "tree_audit.hpp"
 #include "tree_compact.hpp"
 #include "tree_copy.hpp"
 
@@ -5180,6 +5181,204 @@ __global__ __launch_bounds__(256) void k_verify_list_branches(
     const uint32_t* rt = reinterpret_cast<const uint32_t*>(roots + (root_stride ? 32 * g : 0));
     ok[g] = (v0.x == rt[0] && v0.y == rt[1] && v0.z == rt[2] && v0.w == rt[3] && v1.x == rt[4] && v1.y == rt[5] &&
              v1.z == rt[6] && v1.w == rt[7]);
+}
+
+// ----------------------------------------------------------------------------
+// Audit of resident trees: is every stored node what the level
+// below it says?  A stored level-d node is checked against the STORED level
+// d - 1, so nothing depends on anything the launch computes: the work items of
+// tree_audit.hpp -- every node of level 1 .. D and the root of every tree, then
+// the container checks -- are numbered through and a bounded grid strides over
+// them, one Keccak state per lane.  Where a tree's items start, where each of
+// its levels' items start and the two base addresses of every level (the level
+// below it and its own stored nodes) are per-workgroup LDS, filled by one wave
+// per tree, a lane per level.  A window of 256 bytes at a 16-byte aligned
+// address is sixteen 16-byte loads (block 2 after the first permutation, as in
+// hash_window256_split); any other window and the raw chunk under the root of a
+// short list go through sponge_generic, which reads no byte beyond the message.
+// Nodes are 16-byte aligned by contract.  A lane that finds a mismatch adds one
+// to the tree's count and lowers the tree's key, both agent-scope atomics; no
+// other word is written: no hand-off, no arrival counter, no workspace.
+namespace {
+
+// 16 bytes of HBM named as such: an address read back from LDS is otherwise a flat one
+__device__ __forceinline__ uint4 audit_ld16(const uint8_t* p) {
+    const copy_u32x4 v = *reinterpret_cast<const copy_global_u32x4*>((uintptr_t)p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ void audit_window256(const uint8_t* w, uint4& d0, uint4& d1) {
+    State s;
+    uint4 v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = audit_ld16(w + 16 * k);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        s.lo[2 * k] = v[k].x;
+        s.hi[2 * k] = v[k].y;
+        s.lo[2 * k + 1] = v[k].z;
+        s.hi[2 * k + 1] = v[k].w;
+    }
+    s.lo[16] = v[8].x;
+    s.hi[16] = v[8].y;
+    const uint32_t t0 = v[8].z, t1 = v[8].w;
+#pragma unroll
+    for (int k = 17; k < 25; ++k) s.lo[k] = s.hi[k] = 0;
+    keccak_f(s);
+    s.lo[0] ^= t0;
+    s.hi[0] ^= t1;
+    uint4 u[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) u[k] = audit_ld16(w + 16 * (9 + k));
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        s.lo[1 + 2 * k] ^= u[k].x;
+        s.hi[1 + 2 * k] ^= u[k].y;
+        s.lo[2 + 2 * k] ^= u[k].z;
+        s.hi[2 + 2 * k] ^= u[k].w;
+    }
+    s.lo[15] ^= 1u;  // byte 256 = byte 120 of block 1
+    s.hi[16] ^= 0x80000000u;
+    keccak_f_digest(s);
+    digest(s, d0, d1);
+}
+
+__device__ __forceinline__ bool audit_differs(uint4 a0, uint4 a1, uint4 b0, uint4 b1) {
+    return ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) |
+            (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+}
+
+// the rare path: one more bad node of this report, and the smallest (level, index) so far
+__device__ __noinline__ void audit_mismatch(AuditReport* r, uint32_t level, uint64_t index) {
+    (void)__hip_atomic_fetch_add(&r->bad, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_min(&r->key, audit_key(level, index), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kAuditThreads, 4) void k_trees_audit(TreesAuditArgs g) {
+    constexpr uint32_t kSlots = kCopyLevelsMax + 1;      // levels 1 .. D <= 64 and the root
+    __shared__ AuditShape shp[kTreesMax];
+    __shared__ uint64_t tfirst[kTreesMax + 1];          // the call's first item of tree t; [ntrees]: the container's
+    __shared__ uint64_t sfirst[kTreesMax][kSlots + 1];  // tree t's first item of slot s; [slots]: its total
+    __shared__ const uint8_t* schild[kTreesMax][kSlots];  // where slot s's messages start ...
+    __shared__ const uint8_t* snode[kTreesMax][kSlots];   // ... and its stored nodes
+    __shared__ uint32_t scoff[kTreesMax];
+    const uint32_t nt = g.ntrees < kTreesMax ? g.ntrees : kTreesMax;
+    const uint32_t w = threadIdx.x >> 6, L = threadIdx.x & 63u;
+    for (uint32_t t0 = 0; t0 < nt; t0 += kAuditThreads / 64) {
+        const uint32_t t = __builtin_amdgcn_readfirstlane(t0 + w);  // wave-uniform: the descriptor by scalar loads
+        if (t >= nt) continue;
+        const AuditTree& T = g.t[t];
+        const AuditShape b = audit_shape(T.n, T.capacity, T.len0);
+        if (L == 0) {
+            shp[t] = b;
+            scoff[t] = T.coff;
+        }
+        const uint32_t slots = audit_slots(b);
+        for (uint32_t s = L; s <= slots; s += 64) {
+            sfirst[t][s] = audit_slot_first(b, s);
+            if (s == slots) break;
+            uint32_t cb, nb;
+            uint64_t co, no;
+            audit_slot_child(b, s, &cb, &co);
+            audit_slot_node(b, s, &nb, &no);
+            schild[t][s] = (cb == kAuditLevel0 ? T.level0 : T.levels) + co;
+            snode[t][s] = (nb == kAuditRootBuf ? T.root : T.levels) + no;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t a = 0;
+        for (uint32_t t = 0; t < nt; ++t) {
+            tfirst[t] = a;
+            a += sfirst[t][audit_slots(shp[t])];
+        }
+        tfirst[nt] = a;
+    }
+    __syncthreads();
+    const uint64_t in_trees = tfirst[nt], total = in_trees + (g.container ? 1 + nt : 0);
+    const uint64_t stride = (uint64_t)gridDim.x * kAuditThreads;
+    for (uint64_t q = (uint64_t)blockIdx.x * kAuditThreads + threadIdx.x; q < total; q += stride) {
+        uint4 d0, d1, s0, s1;
+        if (q >= in_trees) {  // the container: K(message), then each tree's 32 bytes of it against the tree's root
+            const uint32_t c = (uint32_t)(q - in_trees);
+            const uint32_t *have, *want;
+            if (c == 0) {
+                sponge_generic(g.container, g.container_len, 0u, false, 0, d0, d1);
+                want = reinterpret_cast<const uint32_t*>(g.container_root);
+                have = nullptr;
+            } else {
+                const uint32_t coff = scoff[c - 1];
+                if (coff == 0xffffffffu) continue;  // no field of the container
+                have = reinterpret_cast<const uint32_t*>(g.container + coff);
+                want = reinterpret_cast<const uint32_t*>(snode[c - 1][shp[c - 1].D]);
+                d0 = make_uint4(have[0], have[1], have[2], have[3]);
+                d1 = make_uint4(have[4], have[5], have[6], have[7]);
+            }
+            s0 = make_uint4(want[0], want[1], want[2], want[3]);
+            s1 = make_uint4(want[4], want[5], want[6], want[7]);
+            if (audit_differs(d0, d1, s0, s1)) audit_mismatch(g.reports + nt, kAuditContainer, c);
+            continue;
+        }
+        uint32_t t = 0;
+        while (q >= tfirst[t + 1]) ++t;  // q < tfirst[nt]
+        const uint64_t r = q - tfirst[t];
+        const AuditShape& b = shp[t];
+        uint32_t lo = 0, hi = b.D;  // the last slot that starts at or below r (audit_slot_of, over the LDS copy)
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (sfirst[t][mid] <= r)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        const AuditItem it = audit_item_in(b, lo, r - sfirst[t][lo]);
+        const uint8_t* src = schild[t][lo] + it.child_off;
+        const uint8_t* node = snode[t][lo] + it.node_off;
+        if (it.level == 1) {
+            if (it.msg_len == 256u && it.zeros == 0u && (((uintptr_t)src) & 15u) == 0)
+                audit_window256(src, d0, d1);
+            else
+                sponge_generic(src, it.msg_len, it.zeros, false, 0, d0, d1);
+        } else if (it.child_buf == kAuditLevel0) {  // the root of a list of at most one chunk
+            sponge_generic(src, it.msg_len, it.zeros, true, b.n, d0, d1);
+        } else {  // two nodes, a node and 0^128, or the top node and the length
+            const uint4 l0 = audit_ld16(src), l1 = audit_ld16(src + 16);
+            uint4 r0 = make_uint4((uint32_t)b.n, (uint32_t)(b.n >> 32), 0u, 0u), r1 = make_uint4(0u, 0u, 0u, 0u);
+            if (it.msg_len == 64u) {
+                r0 = audit_ld16(src + 32);
+                r1 = audit_ld16(src + 48);
+            }
+            hash_pair(l0, l1, r0, r1, it.zeros != 0u, d0, d1);
+        }
+        s0 = audit_ld16(node);
+        s1 = audit_ld16(node + 16);
+        if (audit_differs(d0, d1, s0, s1)) audit_mismatch(g.reports + t, it.level, it.index);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_audit_compare(const uint4* __restrict__ fresh, const uint4* __restrict__ stored,
+                                                       uint64_t first, uint64_t m, AuditReport* report) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    if (audit_differs(fresh[2 * i], fresh[2 * i + 1], stored[2 * (first + i)], stored[2 * (first + i) + 1]))
+        audit_mismatch(report, 0u, first + i);
+}
+
+__global__ __launch_bounds__(64) void k_audit_reports(AuditReport* reports, uint32_t count, uint32_t finish) {
+    const uint32_t i = threadIdx.x;
+    if (i >= count) return;
+    AuditReport& r = reports[i];
+    if (!finish) {
+        r.bad = 0;
+        r.key = kAuditKeyNone;
+        r.first_level = kAuditNone;
+        r.pad = 0;
+    } else if (r.key != kAuditKeyNone) {
+        r.first_level = (uint32_t)(r.key >> kAuditKeyShift);
+        r.key &= (1ull << kAuditKeyShift) - 1;
+    }
 }
 
 }  // namespace mk

@@ -285,4 +285,38 @@ constexpr uint32_t kCopyUnroll = 4;     // 16-byte pieces a thread has in flight
 // a bounded grid striding over the 16-byte pieces of all the trees; every thread writes only its own pieces
 __global__ void k_trees_copy(TreesCopyArgs g);
 
+// Audit of up to kTreesMax resident trees and their container (tree_audit_api.cpp; the work-item
+// map: tree_audit.hpp): every stored node of level >= 1, every root and the container checks in one launch.
+// The descriptors by value, 0.8 KB of kernel arguments; nothing but the reports is written.
+struct AuditTree {
+    const uint8_t *level0, *levels, *root;  // level 0: the items of a list tree, else the 32-B roots / digests
+    uint64_t n, capacity;
+    uint32_t len0;  // bytes of a level-0 entry: 1 .. 128
+    uint32_t coff;  // the root's offset in the container message, 0xffffffff: none
+};
+// a report as the kernels keep it until k_audit_reports(finish) unpacks the key: mk_audit_report's 24 bytes
+struct AuditReport {
+    uint64_t bad;
+    uint64_t key;  // audit_key(level, index) of the first mismatch, kAuditKeyNone: none; then first_index
+    uint32_t first_level, pad;
+};
+struct TreesAuditArgs {
+    AuditTree t[kTreesMax];
+    const uint8_t* container;       // the hash message, 4-B aligned; NULL: no container
+    const uint8_t* container_root;  // 32 bytes
+    AuditReport* reports;           // ntrees + 1, the last the container's
+    uint32_t container_len;
+    uint32_t ntrees;
+};
+constexpr uint32_t kAuditThreads = 256;
+// a bounded grid striding over the work items of all the trees, one Keccak state per lane
+__global__ void k_trees_audit(TreesAuditArgs g);
+// level 0 of a struct / bytes tree: entries [first, first + m) of the stored level 0 against the m freshly
+// hashed ones in `fresh` (the bounded workspace), 32 bytes each; a mismatch goes into *report
+__global__ void k_audit_compare(const uint4* fresh, const uint4* stored, uint64_t first, uint64_t m,
+                                AuditReport* report);
+// count reports: finish == 0 clears them before the checks, finish == 1 unpacks every key into (first_level,
+// first_index) after them
+__global__ void k_audit_reports(AuditReport* reports, uint32_t count, uint32_t finish);
+
 }  // namespace mk

@@ -314,6 +314,31 @@ int trees_copy_check(const mk_tree_copy* trees, uint32_t ntrees, const void* d_s
 int trees_copy_launch(const mk_tree_copy* trees, uint32_t ntrees, const void* d_src_extra32, void* d_dst_extra32,
                       hipStream_t st);
 
+// ---- the audit of resident trees (tree_audit_api.cpp) ----------------------------
+// mk_dev_ssz_trees_audit in three steps, shared with the handles: trees_audit_prepare checks every tree's own
+// arguments and parses the record layouts (layouts, when given, holds a parsed layout per tree or null and is
+// taken instead of the tree's `fields`), trees_audit_check the rest of the call (no device needed for either),
+// trees_audit_launch enqueues the chain on st.
+struct AuditCall {
+    std::vector<StructTreeLayout> own;           // the layouts parsed here
+    const StructTreeLayout* L[MK_TREES_MAX] = {};  // tree i's (STRUCT), else null
+    uint64_t ws = 0;                             // workspace bytes
+    uint64_t items = 0;                          // work items of the call: nodes, roots, level-0 entries, container
+};
+int trees_audit_prepare(const mk_tree_audit* trees, uint32_t ntrees, const StructTreeLayout* const* layouts,
+                        uint32_t container_len, AuditCall& c);
+int trees_audit_check(const mk_tree_audit* trees, uint32_t ntrees, const AuditCall& c, const void* d_container,
+                      uint32_t container_len, const void* d_container_root32, const void* d_reports, const void* d_ws,
+                      uint64_t ws_bytes);
+int trees_audit_launch(const mk_tree_audit* trees, uint32_t ntrees, const AuditCall& c, const void* d_container,
+                       uint32_t container_len, const void* d_container_root32, void* d_reports, void* d_ws,
+                       hipStream_t st);
+// a handle's tree as the audit takes it, and the parsed layout of a registry tree's handle (struct_tree_api.cpp)
+mk_tree_audit tree_audit_desc(const TreeHandle& t, uint32_t container_off);
+const StructTreeLayout* struct_tree_layout_of(const TreeHandle& t);
+// one tree's audit: one chain, one read-back
+int tree_audit(TreeHandle* t, mk_audit_report* out);
+
 // ---- several trees in one call (tree_many_api.cpp) ------------------------------------------
 // mk_ssz_trees_update_workspace_bytes with its error, and mk_dev_ssz_trees_update
 // after bind_stream(): every check, then the launches on st

@@ -212,6 +212,7 @@ TreeHandle* struct_tree_handle(const StructTreeLayout& L) {
     return t;
 }
 const TreeKind& struct_tree_kind() { return kStructKind; }
+const StructTreeLayout* struct_tree_layout_of(const TreeHandle& t) { return &layout_of(t); }
 }  // namespace mk::rt
 
 extern "C" {
@@ -371,5 +372,10 @@ int mk_struct_list_tree_reserve(mk_call* call, mk_struct_list_tree* t, uint64_t 
 }
 
 uint64_t mk_struct_list_tree_capacity(const mk_struct_list_tree* t) { return t ? t->cap : 0; }
+
+int mk_struct_list_tree_audit(mk_call* call, mk_struct_list_tree* t, mk_audit_report* out) {
+    Scope S(call);
+    return S.done(tree_audit(t, out));
+}
 
 }  // extern "C"

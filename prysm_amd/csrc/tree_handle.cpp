@@ -429,4 +429,41 @@ int tree_reserve(TreeHandle* t, uint64_t capacity) {
     return MK_OK;
 }
 
+// ---- audit ------------------------------------------------------------------------
+mk_tree_audit tree_audit_desc(const TreeHandle& t, uint32_t container_off) {
+    mk_tree_audit a{};
+    a.kind = t.kind->id;
+    a.item_len = t.item_len;
+    a.d_items = t.items.p;
+    a.d_level0 = t.kind->level0 ? t.level0.p : nullptr;
+    a.d_levels = t.levels.p;
+    a.d_root32 = t.root.p;
+    a.n = t.count;
+    a.capacity = t.cap;
+    a.container_off = container_off;
+    return a;
+}
+
+// The handle's workspace holds the two reports (its front, 256 bytes) and the
+// level-0 piece behind them: the chain of tree_audit_api.cpp, one read-back.
+int tree_audit(TreeHandle* t, mk_audit_report* out) {
+    if (!t || !out) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> tl(t->mu);
+    const mk_tree_audit a = tree_audit_desc(*t, MK_NO_CONTAINER);
+    const StructTreeLayout* L = t->kind->id == MK_TREE_STRUCT ? struct_tree_layout_of(*t) : nullptr;
+    AuditCall c;
+    TRY(trees_audit_prepare(&a, 1, &L, 0, c));
+    TRY(bind_dev(t->dev));
+    hipStream_t st = ctx()->stream;
+    TRY(grow(t->ws, 256 + c.ws));
+    uint8_t* ws = (uint8_t*)t->ws.p;
+    TRY(trees_audit_check(&a, 1, c, nullptr, 0, nullptr, ws, ws + 256, c.ws));
+    TRY(trees_audit_launch(&a, 1, c, nullptr, 0, nullptr, ws, ws + 256, st));
+    mk_audit_report both[2];
+    HIPCHK(hipMemcpyAsync(both, ws, sizeof both, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *out = both[0];
+    return MK_OK;
+}
+
 }  // namespace mk::rt

@@ -487,9 +487,48 @@ int set_reserve(mk_tree_set* s, uint32_t tree, uint64_t capacity) {
     return MK_OK;
 }
 
+// ---- audit ------------------------------------------------------------------------
+// Everything pending is flushed and waited for, as for a root; then the chain
+// of tree_audit_api.cpp over all the trees and the message as the device holds
+// it, and one read-back of the count + 1 reports.  The set's workspace holds
+// the reports (its front, 512 bytes) and the level-0 piece behind them.
+int set_audit(mk_tree_set* s, mk_audit_report* out) {
+    if (!s || !out) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    const uint32_t nt = (uint32_t)s->trees.size();
+    if (nt == 0) return fail(MK_EINVAL, "a set without trees has nothing to audit");
+    TRY(settle(s));
+    const uint32_t clen = nparts(s) ? s->container_len : 0;
+    mk_tree_audit table[MK_TREES_MAX] = {};
+    const StructTreeLayout* layouts[MK_TREES_MAX] = {};
+    for (uint32_t i = 0; i < nt; ++i) {
+        const mk_tree_set::Tree& t = s->trees[i];
+        table[i] = tree_audit_desc(*t.h, clen ? t.coff : MK_NO_CONTAINER);
+        if (t.kind == MK_TREE_STRUCT) layouts[i] = struct_tree_layout_of(*t.h);
+    }
+    AuditCall c;
+    TRY(trees_audit_prepare(table, nt, layouts, clen, c));
+    TRY(bind_set(s));
+    hipStream_t st = ctx()->stream;
+    TRY(grow(s->ws, 512 + c.ws));
+    uint8_t* ws = (uint8_t*)s->ws.p;
+    const void* msg = clen ? s->stage.p : nullptr;
+    const void* croot = clen ? s->croot.p : nullptr;
+    TRY(trees_audit_check(table, nt, c, msg, clen, croot, ws, ws + 512, c.ws));
+    TRY(trees_audit_launch(table, nt, c, msg, clen, croot, ws, ws + 512, st));
+    HIPCHK(hipMemcpyAsync(out, ws, (nt + 1) * sizeof(mk_audit_report), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mk_tree_set_audit(mk_call* call, mk_tree_set* s, mk_audit_report* out) {
+    Scope S(call);
+    return S.done(set_audit(s, out));
+}
 
 int mk_tree_set_clone(mk_call* call, mk_tree_set* src, mk_tree_set** out) {
     Scope S(call);

@@ -938,6 +938,93 @@ def trees_copy(trees, extra_src: torch.Tensor = None, extra_dst: torch.Tensor = 
                 _p(extra_dst) if extra_dst is not None else None, _stream(some.device), device=_dev(some))
 
 
+class TreeAuditArgs:
+    """One tree of ``trees_audit`` (mk_tree_audit): the ``n`` values of a built
+    tree of ``kind`` laid out for ``capacity`` values.  ``level0``: the struct
+    roots / element digests of a STRUCT / BYTES tree (None for a list tree);
+    ``spec`` the field layout (STRUCT); ``container_off`` the byte offset of the
+    tree's root in the container message, None: not a field of it."""
+
+    def __init__(self, kind: int, items: torch.Tensor, n: int, capacity: int, item_len: int, levels: torch.Tensor,
+                 root: torch.Tensor, level0: torch.Tensor = None, spec=None, container_off: int = None):
+        self.kind, self.items, self.n, self.capacity, self.item_len = kind, items, n, capacity, item_len
+        self.levels, self.root, self.level0, self.spec, self.container_off = levels, root, level0, spec, container_off
+
+
+def _audit_table(trees):
+    from .registry import _fields
+
+    arr = (_lib.TreeAudit * max(len(trees), 1))()
+    keep = []
+    for a, t in zip(arr, trees):
+        leaf = t.item_len if t.kind == _lib.MK_TREE_LIST else 32
+        if t.items is not None and t.items.numel() * t.items.element_size() < t.n * t.item_len:
+            raise ValueError("value buffer shorter than n * item_len")
+        if t.level0 is not None and t.level0.numel() * t.level0.element_size() < 32 * t.n:
+            raise ValueError("level-0 buffer shorter than 32 * n")
+        if t.levels is not None and t.levels.numel() * t.levels.element_size() < list_tree_levels_bytes(t.capacity, leaf):
+            raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, leaf length)")
+        if t.root is not None and t.root.numel() * t.root.element_size() < 32:
+            raise ValueError("root buffer shorter than 32 bytes")
+        a.kind, a.item_len, a.n, a.capacity = t.kind, t.item_len, t.n, t.capacity
+        a.d_items = t.items.data_ptr() if t.items is not None else None
+        a.d_level0 = t.level0.data_ptr() if t.level0 is not None else None
+        a.d_levels = t.levels.data_ptr() if t.levels is not None else None
+        a.d_root32 = t.root.data_ptr() if t.root is not None else None
+        if t.spec is not None:
+            f = _fields(t.spec)
+            keep.append(f)
+            a.fields, a.nfields = ctypes.cast(f, ctypes.c_void_p), len(t.spec)
+        a.container_off = _lib.MK_NO_CONTAINER if t.container_off is None else t.container_off
+    return arr, keep
+
+
+def trees_audit_workspace_bytes(trees) -> int:
+    """Workspace of ``trees_audit`` over ``trees`` (0: list trees only, or a list it would refuse)."""
+    arr, _keep = _audit_table(trees)
+    return _lib.load().mk_ssz_trees_audit_workspace_bytes(arr, len(trees))
+
+
+def trees_audit(trees, container: torch.Tensor = None, container_len: int = 0, container_root: torch.Tensor = None,
+                reports: torch.Tensor = None, ws: torch.Tensor = None) -> torch.Tensor:
+    """Audit up to 16 built resident trees (``TreeAuditArgs``) and, with
+    ``container_len`` > 0, the hash message that holds their roots: every
+    stored node against what is stored below it, read-only, on the current
+    stream (mk_dev_ssz_trees_audit).  Returns ``reports``, a
+    device tensor of 24 * (len(trees) + 1) bytes -- one mk_audit_report per
+    tree, then the container's; ``audit_reports`` turns it into tuples.
+    Nothing is allocated when ``reports`` and ``ws`` are given: the call can
+    be captured."""
+    if not trees:
+        raise ValueError("no trees")
+    dev_t = trees[0].root.device
+    arr, _keep = _audit_table(trees)
+    if ws is None:
+        ws = torch.empty(max(_lib.load().mk_ssz_trees_audit_workspace_bytes(arr, len(trees)), 16), dtype=torch.uint8,
+                         device=dev_t)
+    if reports is None:
+        reports = torch.empty(24 * (len(trees) + 1), dtype=torch.uint8, device=dev_t)
+    if reports.numel() * reports.element_size() < 24 * (len(trees) + 1):
+        raise ValueError("reports shorter than 24 * (len(trees) + 1) bytes")
+    if container_len and (container is None or container.numel() < container_len or container_root is None or
+                          container_root.numel() < 32):
+        raise ValueError("container shorter than container_len, or no 32-B container root")
+    _lib.invoke("mk_dev_ssz_trees_audit", arr, len(trees), _p(container) if container_len else None, container_len,
+                _p(container_root) if container_len else None, _p(reports), _p(ws), ws.numel(), _stream(dev_t),
+                device=_dev(trees[0].root))
+    return reports
+
+
+def audit_reports(reports: torch.Tensor):
+    """``trees_audit``'s device reports as host tuples ``(bad, first_level, first_index)`` (synchronises)."""
+    raw = np.ascontiguousarray(reports.cpu().numpy()).view(np.uint8).reshape(-1, 24)
+    out = []
+    for r in raw:
+        bad, idx = (int(x) for x in r[:16].copy().view(np.uint64))
+        out.append((bad, int(r[16:20].copy().view(np.uint32)[0]), idx))
+    return out
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

@@ -180,6 +180,18 @@ class _Tree:
         ``capacity`` than the current one does nothing."""
         self._call("reserve", int(capacity))
 
+    def audit(self):
+        """Check every stored node of the tree against what is stored below it
+        -- level 0 against the values, each level against the one below, the
+        root against the top and the length -- on the device, read-only
+        (DESIGN.md §5n): ``(bad, first_level, first_index)``, the number of
+        mismatches and the smallest (level, index) among them;
+        ``(0, _lib.MK_AUDIT_NONE, 2**64 - 1)`` for a sound tree.  Level
+        ``_lib.MK_AUDIT_ROOT`` is the root."""
+        out = _lib.AuditReport()
+        self._call("audit", ctypes.byref(out))
+        return out.astuple()
+
 
 def verify_branches(values, indices, n: int, item_len: int, branches, root, container=None,
                     container_off: int = None, device: int = -1) -> np.ndarray:
@@ -423,6 +435,20 @@ class TreeSet:
     def reserve(self, tree, capacity: int) -> None:
         """Room for ``capacity`` values in one tree; pending changes stay pending."""
         self._call("reserve", self._tree(tree), int(capacity))
+
+    def audit(self):
+        """Is every tree what its values say, and the message what the trees
+        say?  Whatever is pending is flushed first, as ``root()`` does; then
+        every stored node of every tree, every root, the roots' 32 bytes in the
+        message and the hash of the message are checked in HBM
+        and len(self) + 1 reports ``(bad, first_level, first_index)`` come
+        back, tree by tree and the container's last (index 0: the hash of the
+        message, 1 + i: tree i's root in it).  All ``(0, MK_AUDIT_NONE, ...)``:
+        the resident state is sound, and a state root that does not match
+        ``root()`` is the block's fault."""
+        out = (_lib.AuditReport * (len(self) + 1))()
+        self._call("audit", out)
+        return [r.astuple() for r in out]
 
     def leaf_len(self, tree) -> int:
         """Bytes of a level-0 entry of a tree: what ``branches`` proves."""
