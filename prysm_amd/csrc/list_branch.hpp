@@ -3,7 +3,7 @@
 // mk_ssz_list_tree_levels_bytes(capacity, s), which list bytes the 256-byte
 // window of item i holds, which stored node is the sibling at level d and
 // whether it exists, and the record stride.  Shared by k_list_tree_branches
-// and k_verify_list_branches (merkle_kernels.hip), the host side
+// and k_verify_list_branches (kernels_tree.hip), the host side
 // (tree_branch_api.cpp) and the host fuzz (tests/c_abi/list_branch_fuzz.cpp);
 // no HIP in it.
 #pragma once

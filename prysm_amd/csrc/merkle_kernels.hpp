@@ -177,7 +177,7 @@ __global__ void k_many_level(const uint8_t* items, const ManyList* lists, const 
 __global__ void k_many_final(const uint8_t* items, const ManyList* lists, uint32_t nlists, const uint4* tops,
                              uint4* roots);
 __global__ void k_synth(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t word0);
-// device-resident list tree (merkle_kernels.hip, list_tree_api.cpp)
+// device-resident list tree (kernels_tree.hip, list_tree_api.cpp)
 struct ListTreeArgs {
     const uint8_t* items;  // level 0: n_new items of item_len bytes
     uint32_t* levels;      // level d >= 1 at node sum_{1<=i<d} ceil(cap_chunks / 2^i)

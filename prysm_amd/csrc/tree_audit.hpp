@@ -14,7 +14,7 @@
 // last, and a call numbers its trees one after the other.  Every count comes
 // from n alone; the capacity only places the levels.  No node at or beyond a
 // level's count and no level-0 byte at or beyond n * len0 belongs to any item.
-// Shared by k_trees_audit (merkle_kernels.hip), the host side
+// Shared by k_trees_audit (kernels_tree.hip), the host side
 // (tree_audit_api.cpp) and the host fuzz (tests/c_abi/tree_audit_fuzz.cpp); no
 // HIP in it.
 #pragma once

@@ -3,7 +3,7 @@
 // position q of the n_old - k survivors takes the value of source q + j, j the
 // number of i with r_i - i <= q (r_i - i is non-decreasing: the survivors in
 // front of r_i).  Positions below r_0 do not move (j == 0).  Shared by
-// k_tree_compact (merkle_kernels.hip) and the host fuzz
+// k_tree_compact (kernels_tree.hip) and the host fuzz
 // (tests/c_abi/tree_compact_fuzz.cpp); no HIP in it.
 #pragma once
 #include <stdint.h>

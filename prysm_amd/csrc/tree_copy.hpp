@@ -9,7 +9,7 @@
 // destination offsets differ when the capacities do; everything else starts
 // its buffer.  Levels above D and nodes beyond a level's count belong to no
 // segment: they are not read and not written (§5k).  Shared by k_trees_copy
-// (merkle_kernels.hip), the host side (tree_copy_api.cpp) and the host fuzz
+// (kernels_tree.hip), the host side (tree_copy_api.cpp) and the host fuzz
 // (tests/c_abi/tree_copy_fuzz.cpp); no HIP in it.
 #pragma once
 #include <stdint.h>

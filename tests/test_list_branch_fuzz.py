@@ -36,7 +36,7 @@ def test_arithmetic_has_no_hip_and_is_the_kernels():
     with open(os.path.join(CSRC, "list_branch.hpp")) as f:
         src = f.read()
     assert "#include <hip" not in src and "runtime.hpp" not in src
-    with open(os.path.join(CSRC, "merkle_kernels.hip")) as f:
+    with open(os.path.join(CSRC, "kernels_tree.hip")) as f:
         kern = f.read()
     assert '#include "list_branch.hpp"' in kern
     gather = kern[kern.index("void k_list_tree_branches("):]

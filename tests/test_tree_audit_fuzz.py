@@ -41,7 +41,7 @@ def test_arithmetic_has_no_hip_and_is_the_kernels():
     assert '#include "list_branch.hpp"' in src and '#include "tree_copy.hpp"' in src
     for fn in ("branch_shape(", "branch_window(", "branch_window_padded(", "branch_level_count(", "copy_level_off("):
         assert fn in src, fn
-    with open(os.path.join(CSRC, "merkle_kernels.hip")) as f:
+    with open(os.path.join(CSRC, "kernels_tree.hip")) as f:
         kern = f.read()
     assert '#include "tree_audit.hpp"' in kern
     audit = kern[kern.index("void k_trees_audit("):]
@@ -49,6 +49,7 @@ def test_arithmetic_has_no_hip_and_is_the_kernels():
     for fn in ("audit_shape(", "audit_slot_first(", "audit_slot_child(", "audit_slot_node(", "audit_item_in("):
         assert fn in audit, fn
     assert "g_arrive" not in audit
+    assert "g_arrive" not in kern  # the arrival counters stay with the fused tops (merkle_kernels.hip)
     with open(os.path.join(CSRC, "tree_audit_api.cpp")) as f:
         host = f.read()
     assert '#include "tree_audit.hpp"' in host and "audit_items(" in host and "audit_shape(" in host

@@ -36,7 +36,7 @@ def test_index_map_has_no_hip_and_is_the_kernels():
     with open(os.path.join(CSRC, "tree_compact.hpp")) as f:
         src = f.read()
     assert "#include <hip" not in src and "runtime.hpp" not in src
-    with open(os.path.join(CSRC, "merkle_kernels.hip")) as f:
+    with open(os.path.join(CSRC, "kernels_tree.hip")) as f:
         kern = f.read()
     assert '#include "tree_compact.hpp"' in kern
     body = kern[kern.index("void k_tree_compact("):]
