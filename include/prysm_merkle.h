@@ -96,6 +96,12 @@ int mk_dev_hash_batch_var(mk_call* call, const void* d_in, const uint64_t* d_off
  * list TreeHash builds has uniform element length).  out = 32-B result.
  * item_len == 0 with n > 0 is the reference's divide-by-zero panic: MK_EINVAL. */
 int mk_ssz_merkle_hash(mk_call* call, const uint8_t* items, uint64_t n, uint32_t item_len, uint8_t out[32]);
+/* Workspace of mk_dev_ssz_merkle_hash, exact: one byte less is MK_ENOMEM
+ * before anything is launched, whatever the alignment of d_items and d_ws
+ * (items that are not 16-B aligned never need more).  A 16-B aligned d_ws lets
+ * lists of 17 .. 4096 first-level windows take the latency list tree; any
+ * other d_ws takes the planner's passes to the same root.  With at most one
+ * chunk nothing is read from the workspace (the query still returns 256). */
 uint64_t mk_ssz_merkle_workspace_bytes(uint64_t n, uint32_t item_len);
 int mk_dev_ssz_merkle_hash(mk_call* call, const void* d_items, uint64_t n, uint32_t item_len, void* d_out32,
                            void* d_ws, uint64_t ws_bytes, void* stream);
@@ -126,8 +132,8 @@ int mk_ssz_merkle_many(mk_call* call, const uint8_t* items, const uint64_t* offs
  * digests.  One call, no host round trip: with 32-B elements (16-B aligned)
  * the digests are computed inside the tree's leaf pass and never reach HBM.
  * Workspace from mk_ssz_tree_hash_bytes_list_workspace_bytes (for a 16-B
- * aligned d_elems; other alignments need the two-phase size, n*32 + the
- * plan's, and report MK_ENOMEM when the workspace is short). */
+ * aligned d_elems; other alignments take the two-phase form and need that
+ * size plus n*32 rounded up to 256, and report MK_ENOMEM below it). */
 uint64_t mk_ssz_tree_hash_bytes_list_workspace_bytes(uint64_t n, uint32_t elem_len);
 int mk_dev_ssz_tree_hash_bytes_list(mk_call* call, const void* d_elems, uint64_t n, uint32_t elem_len,
                                     void* d_out32, void* d_ws, uint64_t ws_bytes, void* stream);
@@ -288,7 +294,12 @@ int mk_ssz_merkle_shard_plan(mk_call* call, uint64_t n, uint32_t item_len, uint3
                              uint32_t* nonempty, uint64_t* item_begin);
 /* Root (32 B, height `height` above the chunks) of one shard.  pad_at_one=1
  * for every shard of a tree with >1 non-empty shard: a ragged last shard keeps
- * applying the reference's odd rule (node || 0^128) up to `height`. */
+ * applying the reference's odd rule (node || 0^128) up to `height`.
+ * Workspace: mk_ssz_merkle_workspace_bytes(shard_n, item_len), the query of a
+ * merkleHash over the shard's own items -- its plan bounds the subtree plan at
+ * every height, pad_at_one and alignment; less is MK_ENOMEM before any launch.
+ * The query is not monotonic in n: a workspace shared by shards of different
+ * sizes takes the largest of their queries. */
 int mk_dev_ssz_merkle_subtree(mk_call* call, const void* d_shard_items, uint64_t shard_n, uint32_t item_len,
                               uint32_t height, int pad_at_one, void* d_out32, void* d_ws, uint64_t ws_bytes,
                               void* stream);
@@ -298,7 +309,12 @@ int mk_dev_ssz_merkle_subtree(mk_call* call, const void* d_shard_items, uint64_t
  * gets the count).  The shards' frontiers, concatenated in shard order, are
  * that level of the whole tree, so ranks gather a few KB each and the top
  * levels move to the finisher (mk_dev_ssz_merkle_finish_nodes), which can
- * overlap the ranks' next Merkleization.  0 < frontier_log2 < height. */
+ * overlap the ranks' next Merkleization.  0 < frontier_log2 < height; a
+ * frontier one level above the chunks (frontier_log2 == height - 1) of a shard
+ * of more than 2^17 first-level windows is MK_EINVAL.  d_out holds 32 <<
+ * frontier_log2 bytes, of which only the first 32 * *nodes_out are written.
+ * Workspace: mk_ssz_merkle_workspace_bytes(shard_n, item_len), as for
+ * mk_dev_ssz_merkle_subtree (it bounds every frontier plan too). */
 int mk_dev_ssz_merkle_subtree_frontier(mk_call* call, const void* d_shard_items, uint64_t shard_n,
                                        uint32_t item_len, uint32_t height, uint32_t frontier_log2, int pad_at_one,
                                        void* d_out, uint64_t* nodes_out, void* d_ws, uint64_t ws_bytes,

@@ -110,10 +110,6 @@ int launch_top_span(const void* d_nodes, uint64_t c, uint64_t n_items, uint32_t 
 // length mix-in -- where the general plan ran one 1024-thread k_wave3 over
 // the last <= 256 nodes, whose widest levels run as lane pairs at ~14 k
 // cycles each.  C1 0.095 -> 0.085 ms (profiles/r06/c1/).
-uint64_t list_tree_windows(uint64_t n, uint32_t item_len) {
-    if (n == 0 || item_len == 0 || n > (UINT64_MAX / 4) / item_len) return 0;
-    return ceil_div(ceil_div(n * (uint64_t)item_len, mk::chunk_bytes(item_len)), 2);
-}
 int dev_list_tree(const void* d_items, uint64_t n, uint32_t item_len, void* d_out32, uint8_t* ws,
                   hipStream_t st) {
     if (inject_ehip()) return fail(MK_EHIP, "hipLaunchKernelGGL: injected failure (MK_INJECT_EHIP)");
@@ -184,10 +180,17 @@ int dev_tree_hash_elems(const void* d_elems, uint64_t n, uint32_t elem_len, void
                         uint64_t ws_bytes, hipStream_t st) {
     if (!d_out32 || (n && elem_len && !d_elems)) return fail(MK_EINVAL, "null pointer");
     ElemPlan e;
-    TRY(make_elem_plan(n, elem_len, ((uintptr_t)d_elems % 16) == 0, e));
-    if (ws_bytes < e.ws_bytes)
+    const bool aligned16 = ((uintptr_t)d_elems % 16) == 0;
+    TRY(make_elem_plan(n, elem_len, aligned16, e));
+    uint64_t need = e.ws_bytes;
+    if (!aligned16) {  // the documented two-phase size: the query's plus the digest array
+        ElemPlan q;
+        TRY(make_elem_plan(n, elem_len, true, q));
+        need = std::max<uint64_t>(need, q.ws_bytes + align256(32 * n));
+    }
+    if (ws_bytes < need)
         return fail(MK_ENOMEM, "workspace too small: %llu < %llu", (unsigned long long)ws_bytes,
-                    (unsigned long long)e.ws_bytes);
+                    (unsigned long long)need);
     if (n && !d_ws) return fail(MK_EINVAL, "null workspace");
     if (e.fused) return launch_plan(e.p, (const uint8_t*)d_elems, (uint8_t*)d_out32, (uint8_t*)d_ws, ws_bytes, st);
     uint8_t* dig = (uint8_t*)d_ws;
@@ -444,23 +447,29 @@ int launch_plan(const Plan& p, const uint8_t* d_items, uint8_t* d_out32, uint8_t
     return MK_OK;
 }
 
-bool list_tree_ok(uint64_t n, uint32_t item_len) {
-    const uint64_t c1 = list_tree_windows(n, item_len);
-    return c1 > 16 && c1 <= 4096;
-}
-uint64_t list_tree_ws(uint64_t n, uint32_t item_len) {
-    if (!list_tree_ok(n, item_len)) return 0;
-    const uint64_t c4 = ceil_div(list_tree_windows(n, item_len), 8);
-    return align256(32 * c4) + align256(32 * ceil_div(c4, 16));
+bool list_tree_ok(uint64_t n, uint32_t item_len) { return mk::list_tree_fits(n, item_len); }
+uint64_t list_tree_ws(uint64_t n, uint32_t item_len) { return mk::list_tree_ws_bytes(n, item_len); }
+
+int ws_too_small(uint64_t ws_bytes, uint64_t need) {
+    return fail(MK_ENOMEM, "workspace too small: %llu < %llu", (unsigned long long)ws_bytes, (unsigned long long)need);
 }
 
+// The workspace contract is the query's size whatever the pointers' alignment:
+// a workspace below mk_ssz_merkle_workspace_bytes is refused before any launch,
+// also where this call's own plan (the list tree's shapes through the planner,
+// items that are not 16-B aligned) would have fitted into less.
 int dev_merkle_hash(const void* d_items, uint64_t n, uint32_t item_len, void* d_out32, void* d_ws, uint64_t ws_bytes,
                     hipStream_t st) {
     if (!d_out32 || (n && item_len && !d_items)) return fail(MK_EINVAL, "null pointer");
-    if (list_tree_ok(n, item_len) && ws_bytes >= list_tree_ws(n, item_len) && (uintptr_t)d_ws % 16 == 0)
-        return dev_list_tree(d_items, n, item_len, d_out32, (uint8_t*)d_ws, st);
+    const bool aligned16 = ((uintptr_t)d_items % 16) == 0;
+    if (list_tree_ok(n, item_len)) {
+        if (ws_bytes < list_tree_ws(n, item_len)) return ws_too_small(ws_bytes, list_tree_ws(n, item_len));
+        if ((uintptr_t)d_ws % 16 == 0) return dev_list_tree(d_items, n, item_len, d_out32, (uint8_t*)d_ws, st);
+    }
     Plan p;
-    TRY(mk::make_plan(n, item_len, false, 0, false, ((uintptr_t)d_items % 16) == 0, p));
+    TRY(mk::make_plan(n, item_len, false, 0, false, aligned16, p));
+    if (!p.small && !aligned16 && ws_bytes < mk::merkle_ws_bytes(n, item_len))
+        return ws_too_small(ws_bytes, mk::merkle_ws_bytes(n, item_len));
     return launch_plan(p, (const uint8_t*)d_items, (uint8_t*)d_out32, (uint8_t*)d_ws, ws_bytes, st);
 }
 
@@ -594,9 +603,7 @@ extern "C" {
 // ---- merkleHash ---------------------------------------------------------------
 uint64_t mk_ssz_merkle_workspace_bytes(uint64_t n, uint32_t item_len) {
     Scope S(nullptr, false);
-    Plan p;
-    if (mk::make_plan(n, item_len, false, 0, false, true, p) != MK_OK) return 0;
-    return std::max<uint64_t>(p.small ? 256 : mk::plan_ws_bytes(p), list_tree_ws(n, item_len));
+    return mk::merkle_ws_bytes(n, item_len);
 }
 
 int mk_dev_ssz_merkle_hash(mk_call* call, const void* d_items, uint64_t n, uint32_t item_len, void* d_out32,
@@ -669,6 +676,8 @@ int mk_dev_ssz_merkle_subtree(mk_call* call, const void* d_shard_items, uint64_t
         if (!d_out32 || (shard_n && !d_shard_items)) return fail(MK_EINVAL, "null pointer");
         Plan p;
         TRY(mk::make_plan(shard_n, item_len, true, height, pad_at_one != 0, ((uintptr_t)d_shard_items % 16) == 0, p));
+        if (ws_bytes < mk::merkle_ws_bytes(shard_n, item_len))
+            return ws_too_small(ws_bytes, mk::merkle_ws_bytes(shard_n, item_len));
         return launch_plan(p, (const uint8_t*)d_shard_items, (uint8_t*)d_out32, (uint8_t*)d_ws, ws_bytes,
                            (hipStream_t)stream);
     });
@@ -683,6 +692,8 @@ int mk_dev_ssz_merkle_subtree_frontier(mk_call* call, const void* d_shard_items,
         Plan p;
         TRY(mk::make_plan(shard_n, item_len, true, height, pad_at_one != 0, ((uintptr_t)d_shard_items % 16) == 0, p,
                           false, frontier_log2));
+        if (ws_bytes < mk::merkle_ws_bytes(shard_n, item_len))
+            return ws_too_small(ws_bytes, mk::merkle_ws_bytes(shard_n, item_len));
         if (nodes_out) *nodes_out = p.out_nodes;
         return launch_plan(p, (const uint8_t*)d_shard_items, (uint8_t*)d_out, (uint8_t*)d_ws, ws_bytes,
                            (hipStream_t)stream);

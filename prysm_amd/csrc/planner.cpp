@@ -257,6 +257,28 @@ int make_plan(uint64_t n, uint32_t item_len, bool subtree, uint32_t height, bool
 
 uint64_t plan_ws_bytes(const Plan& p) { return 32 * (p.slot_nodes[0] + p.slot_nodes[1]) + 256; }
 
+// ---- workspace queries ---------------------------------------------------------------------
+static uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+
+uint64_t list_tree_windows(uint64_t n, uint32_t item_len) {
+    if (n == 0 || item_len == 0 || n > (UINT64_MAX / 4) / item_len) return 0;
+    return ceil_div(ceil_div(n * (uint64_t)item_len, chunk_bytes(item_len)), 2);
+}
+bool list_tree_fits(uint64_t n, uint32_t item_len) {
+    const uint64_t c1 = list_tree_windows(n, item_len);
+    return c1 > 16 && c1 <= 4096;
+}
+uint64_t list_tree_ws_bytes(uint64_t n, uint32_t item_len) {
+    if (!list_tree_fits(n, item_len)) return 0;
+    const uint64_t c4 = ceil_div(list_tree_windows(n, item_len), 8);
+    return align256(32 * c4) + align256(32 * ceil_div(c4, 16));
+}
+uint64_t merkle_ws_bytes(uint64_t n, uint32_t item_len) {
+    Plan p;
+    if (make_plan(n, item_len, false, 0, false, true, p) != MK_OK) return 0;
+    return std::max<uint64_t>(p.small ? 256 : plan_ws_bytes(p), list_tree_ws_bytes(n, item_len));
+}
+
 int shard_plan(uint64_t n, uint32_t item_len, uint32_t nshards, uint32_t* height, uint32_t* nonempty,
                uint64_t* begin) {
     if (nshards == 0) return fail(MK_EINVAL, "nshards == 0");
@@ -299,7 +321,6 @@ uint64_t trie_level_off(uint64_t cap, uint32_t d) {
 uint64_t trie_levels_nodes(uint64_t cap, uint32_t depth) { return trie_level_off(cap, depth + 1); }
 
 // ---- many lists ----------------------------------------------------------------------------
-static uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
 
 int make_many_plan(const uint64_t* offs, const uint64_t* n, const uint32_t* item_len, uint32_t nlists,
                    uint64_t items_bytes, bool base_aligned16, ManyPlan& mp) {

@@ -81,6 +81,19 @@ int make_plan(uint64_t n, uint32_t item_len, bool subtree, uint32_t height, bool
               bool node_input = false, uint32_t frontier = 0, uint64_t mixin_n = 0, bool leaf_ni1 = false);
 uint64_t plan_ws_bytes(const Plan& p);
 
+// ---- workspace queries -------------------------------------------------------
+// The latency list tree (merkle_api.cpp dev_list_tree) takes a merkleHash whose
+// first level has 16 < windows <= 2^12; its workspace holds one node per 8
+// windows and one per 128.  For those shapes it is never below the pass plan's.
+uint64_t list_tree_windows(uint64_t n, uint32_t item_len);
+bool list_tree_fits(uint64_t n, uint32_t item_len);
+uint64_t list_tree_ws_bytes(uint64_t n, uint32_t item_len);  // 0: not that form
+// mk_ssz_merkle_workspace_bytes: the plan of 16-B aligned items, or the list
+// tree's when that is larger (0: a shape make_plan refuses).  It also bounds
+// the plan of the same items at any other alignment and every subtree /
+// frontier plan over them (tests/c_abi/planner_fuzz.cpp holds both).
+uint64_t merkle_ws_bytes(uint64_t n, uint32_t item_len);
+
 int shard_plan(uint64_t n, uint32_t item_len, uint32_t nshards, uint32_t* height, uint32_t* nonempty,
                uint64_t* begin);
 // nodes of a shard `k` levels below its root (>= 1 with pad_at_one)

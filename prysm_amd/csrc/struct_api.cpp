@@ -373,7 +373,9 @@ int mk_dev_ssz_struct_list_root(mk_call* call, const void* d_records, uint64_t n
     return dev_entry(call, stream, [&]() -> int {
         mk::HostSpec sp;
         TRY(make_spec(fields, nfields, record_len, sp));
-        if (ws_bytes < struct_list_ws(n, sp)) return fail(MK_ENOMEM, "workspace too small");
+        if (ws_bytes < struct_list_ws(n, sp))
+            return fail(MK_ENOMEM, "workspace too small: %llu < %llu", (unsigned long long)ws_bytes,
+                        (unsigned long long)struct_list_ws(n, sp));
         if (n && !d_records) return fail(MK_EINVAL, "null pointer");
         uint8_t* ws = (uint8_t*)d_ws;
         uint8_t* msg = ws;
@@ -523,7 +525,9 @@ int mk_dev_ssz_struct_roots(mk_call* call, const void* d_records, uint64_t n, ui
         mk::HostSpec sp;
         TRY(make_spec(fields, nfields, record_len, sp));
         if (n && (!d_records || !d_roots)) return fail(MK_EINVAL, "null pointer");
-        if (ws_bytes < n * (uint64_t)sp.msg_len) return fail(MK_ENOMEM, "workspace too small");
+        if (ws_bytes < n * (uint64_t)sp.msg_len)
+            return fail(MK_ENOMEM, "workspace too small: %llu < %llu", (unsigned long long)ws_bytes,
+                        (unsigned long long)(n * (uint64_t)sp.msg_len));
         return launch_struct_roots(d_records, n, sp, d_ws, d_roots, (hipStream_t)stream);
     });
 }

@@ -57,7 +57,9 @@ int dev_merkle_root(const void* d_data, const uint64_t* d_offs, uint64_t n, uint
                     uint64_t heap_bytes, void* d_leaves32, void* d_out32, hipStream_t st) {
     if (n == 0) return fail(MK_EINVAL, "MerkleRoot of an empty list (reference: index out of range)");
     if (!d_heap || !d_out32 || (!d_offs && !d_data && fixed_len)) return fail(MK_EINVAL, "null pointer");
-    if (heap_bytes < merkle_root_ws(n)) return fail(MK_ENOMEM, "heap workspace too small");
+    if (heap_bytes < merkle_root_ws(n))
+        return fail(MK_ENOMEM, "heap workspace too small: %llu < %llu", (unsigned long long)heap_bytes,
+                    (unsigned long long)merkle_root_ws(n));
     uint8_t* heap = (uint8_t*)d_heap;  // node i at heap + 32 i (node 0 unused)
     uint4* leaves = (uint4*)(heap + 32 * n);
     TRY(dev_leaf_hashes(d_data, d_offs, n, fixed_len, leaves, st));

@@ -75,7 +75,7 @@ def struct_list_root(records: torch.Tensor, n: int, record_len: int, spec, out: 
     if out is None:
         out = torch.empty(32, dtype=torch.uint8, device=records.device)
     if ws is None:
-        ws = torch.empty(_lib.load().mk_ssz_struct_list_workspace_bytes(n, f, len(spec)) + 256, dtype=torch.uint8,
+        ws = torch.empty(_lib.load().mk_ssz_struct_list_workspace_bytes(n, f, len(spec)), dtype=torch.uint8,
                          device=records.device)
     _lib.invoke("mk_dev_ssz_struct_list_root", _p(records), n, record_len, f, len(spec), _p(out), _p(ws), ws.numel(),
                 _stream(records.device), device=dev)
@@ -255,8 +255,9 @@ def shard_plan(n: int, item_len: int, nshards: int):
 
 
 def subtree_workspace(shard_n: int, item_len: int, device) -> torch.Tensor:
-    # the full-tree plan of the same item count bounds the subtree plan
-    nbytes = _lib.load().mk_ssz_merkle_workspace_bytes(max(shard_n, 1), item_len) + 4096
+    # the header's rule: the merkleHash query of the shard's own items bounds every subtree and
+    # frontier plan over them (held by tests/c_abi/planner_fuzz.cpp), and the entries refuse less
+    nbytes = _lib.load().mk_ssz_merkle_workspace_bytes(max(shard_n, 1), item_len)
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 

@@ -2,7 +2,8 @@
 // g++ -fsanitize=address,undefined by tests/test_planner_fuzz.py.  For random
 // (n, item_len, height, frontier, pad_at_one) it builds merkleHash, subtree,
 // frontier and node-input plans, the shard plan, the many-lists plan and the
-// deposit-trie layout, checks their internal invariants (abort on violation)
+// deposit-trie layout, checks their internal invariants (abort on violation),
+// among them the subtree workspace rule of include/prysm_merkle.h,
 // and prints one line per case for the Python restatements
 // (tests/test_distributed.py::_plan_cpu, parallel.frontier_count):
 //   S n item_len world h nonempty b0 .. bworld
@@ -29,6 +30,7 @@ using namespace mk;
 // (1 when cin == 1 and no pad_at_one), then `levels - 1` more halvings.
 static uint64_t g_lock_passes = 0;
 static uint64_t g_node_lock_passes = 0;
+static uint64_t g_subtree_rule = 0, g_subtree_tight = 0;  // accepted subtree plans; those as large as the query
 
 static uint64_t replay(const Plan& p, uint64_t nchunks, bool pad) {
     uint64_t c = nchunks;
@@ -126,6 +128,34 @@ int main(int argc, char** argv) {
                             (unsigned long long)fp.out_nodes);
             }
         }
+        // the subtree workspace rule: whatever subtree / frontier plan the
+        // planner accepts over (shard_n, item_len), at either alignment, fits
+        // the workspace of the full merkleHash plan of the same items at 16-B
+        // alignment, hence mk_ssz_merkle_workspace_bytes(shard_n, item_len)
+        // (merkle_ws_bytes: that plan, or the list tree's when larger)
+        for (int rep = 0; rep < 8; ++rep) {
+            const uint64_t sn = rep < 4 && n ? n : pick(1, 1ull << 22);
+            const uint32_t sil = rep % 2 ? il : 32;
+            const uint64_t sch = ceil_div(sn * (uint64_t)sil, chunk_bytes(sil));
+            const uint32_t lo = levels_to_one(sch);
+            const uint32_t sh = rng() % 4 == 0 ? (uint32_t)pick(1, 40) : lo + (uint32_t)pick(0, 2);
+            const uint32_t sk = rng() % 2 && sh > 1 ? (uint32_t)pick(1, sh - 1) : 0;
+            const bool spad = rng() & 1, sal = rng() & 1;
+            Plan full, fu, sub;
+            REQUIRE(make_plan(sn, sil, false, 0, false, true, full) == MK_OK);
+            REQUIRE(make_plan(sn, sil, false, 0, false, false, fu) == MK_OK);
+            const uint64_t full_ws = full.small ? 256 : plan_ws_bytes(full);
+            const uint64_t query = merkle_ws_bytes(sn, sil);
+            REQUIRE(query >= full_ws && query >= list_tree_ws_bytes(sn, sil));
+            REQUIRE(query == full_ws || query == list_tree_ws_bytes(sn, sil));
+            REQUIRE(fu.small || plan_ws_bytes(fu) <= full_ws);  // unaligned items never need more
+            if (list_tree_fits(sn, sil)) REQUIRE(list_tree_ws_bytes(sn, sil) >= full_ws);
+            if (make_plan(sn, sil, true, sh, spad, sal, sub, false, sk) != MK_OK) continue;
+            ++g_subtree_rule;
+            REQUIRE(plan_ws_bytes(sub) <= full_ws);
+            REQUIRE(plan_ws_bytes(sub) <= query);
+            if (plan_ws_bytes(sub) == query) ++g_subtree_tight;
+        }
         // node-input finisher plan over a gathered level
         const uint64_t cnt = pick(2, 1ull << 16);
         Plan np;
@@ -190,7 +220,13 @@ int main(int argc, char** argv) {
     uint32_t h, ne;
     uint64_t b[2];
     REQUIRE(shard_plan(5, 32, 0, &h, &ne, b) == MK_EINVAL);
-    std::fprintf(stderr, "planner fuzz: %d cases clean (%llu phase-locked leaf passes, %llu node passes)\n", cases,
-                 (unsigned long long)g_lock_passes, (unsigned long long)g_node_lock_passes);
+    // the rule is exercised, and it is not slack everywhere: a query 32 bytes
+    // short would fail the cases where the subtree plan is as large as it
+    REQUIRE(g_subtree_rule > (uint64_t)cases && g_subtree_tight > 0);
+    std::fprintf(stderr,
+                 "planner fuzz: %d cases clean (%llu phase-locked leaf passes, %llu node passes, %llu subtree "
+                 "workspaces, %llu at the bound)\n",
+                 cases, (unsigned long long)g_lock_passes, (unsigned long long)g_node_lock_passes,
+                 (unsigned long long)g_subtree_rule, (unsigned long long)g_subtree_tight);
     return 0;
 }

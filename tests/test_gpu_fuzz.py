@@ -1,7 +1,9 @@
 """Seeded random shapes through every device path against the CPU oracle
 (oracle/: C restatement of hash.go / deposit_trie.go / merkleRoot.go):
-merkleHash at random sizes, item lengths and byte offsets (every planner
-branch: spread leaf passes, lane-pair passes, fused throughput passes),
+merkleHash at random sizes, item lengths and byte offsets (a case is capped
+at 3 MiB and 2^17.5 items, at most 16,384 windows: the spread leaf pass, the
+list tree and the lane-pair k_wave3 passes; the throughput leaf passes start
+above 2^17 windows and belong to tests/test_gpu_ws_contract.py),
 many lists per call, struct roots of random layouts (both struct kernels
 and the generic one), deposit tries grown by random batches with the
 per-log check, and MerkleRoot.  Sizes keep the oracle to seconds.

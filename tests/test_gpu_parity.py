@@ -157,7 +157,10 @@ def test_dev_merkle_item_sizes(gpu, item_len, n):
 
 
 def test_dev_merkle_unaligned_input(gpu):
-    """An input pointer that is not 16-B aligned takes the generic path."""
+    """An input pointer that is not 16-B aligned: 70,001 items are 8,751
+    windows, a k_wave3 leaf pass reading unaligned windows (not the generic
+    k_reduce pass, which the planner picks above 2^17 windows only:
+    tests/test_gpu_ws_contract.py::test_merkle_hash_wide_generic runs that)."""
     import torch
 
     from oracle import oracle as O
