@@ -987,6 +987,89 @@ int mk_struct_list_tree_audit(mk_call* call, mk_struct_list_tree* t, mk_audit_re
 int mk_bytes_list_tree_audit(mk_call* call, mk_bytes_list_tree* t, mk_audit_report* out);
 int mk_tree_set_audit(mk_call* call, mk_tree_set* s, mk_audit_report* out);
 
+/* ---- two resident trees diffed on the device ---------------------- */
+/* Which values of two resident trees differ?  Two stored trees that agree at a
+ * node agree on everything under it, so the differing values are found by
+ * walking down only through nodes that differ: about (differences) x (depth)
+ * node reads whatever n is.  len0 = item_len for MK_TREE_LIST and 32 for
+ * MK_TREE_STRUCT / _BYTES, p = 128 / len0 leaves per chunk, nchunks_X =
+ * ceil(n_X / p), D_X the smallest d with ceil(nchunks_X / 2^d) == 1; level d of
+ * tree X starts at node sum_{1<=i<d} ceil(cap_chunks_X / 2^i) of its level
+ * array, so every offset is taken per side.  With m = min(n_a, n_b):
+ *   the result is the set of indices i < m whose leaf differs -- the item_len
+ *     bytes of item i of a LIST tree, the 32-byte level-0 entry (struct root /
+ *     element digest) of a STRUCT / BYTES tree, so record bytes outside the
+ *     fields and the slack of a VARBYTES slot are no difference.  Indices at or
+ *     above m are never listed: the caller has n_a and n_b;
+ *   node (d, j) covers values [j 2^d p, (j + 1) 2^d p).  It is visited only when
+ *     j 2^d p < m and is comparable when n_a == n_b or (j + 1) 2^d p <= m.  A
+ *     comparable node whose 32 bytes are equal ends the descent; one that is
+ *     not comparable (the straddler of its level when the counts differ) is
+ *     never read and always descended -- with the 0^128 pad of an odd level,
+ *     K(c || 0^128) is both "c was the last chunk" and "an all-zero chunk
+ *     follows c", so a straddler may be equal in two trees of different length;
+ *   no node at or beyond a level's count of its tree, no level above
+ *     min(D_a, D_b) and no leaf byte at or beyond m len0 is read.
+ * mk_dev_ssz_trees_diff diffs up to MK_TREES_MAX pairs: the reports are cleared
+ * on the stream and ONE launch follows (none when no pair has a value below its
+ * m).  Pair i's differing indices go to its d_idx_out in no particular order,
+ * an index only into a slot below max_out; report i holds the exact number of
+ * differing indices, also above max_out, and the smallest one (2^64 - 1: none).
+ * `trees` is host memory, read only during the call: the descriptors travel as
+ * kernel arguments.  Allocates nothing, uploads nothing, needs no workspace,
+ * never synchronises, writes nothing but d_reports and the d_idx_out, and can be
+ * captured into a hipGraph.  The leaves of a LIST tree at any byte alignment;
+ * d_*_level0 (NULL for MK_TREE_LIST) and d_*_levels 16-B aligned, d_idx_out and
+ * d_reports (ntrees reports) 8-B aligned.  d_*_items of a STRUCT / BYTES tree
+ * are not read.  The same buffers on both sides are allowed: the result is empty.
+ * MK_EINVAL, every check before a device is looked up and nothing launched:
+ * ntrees 0 or > MK_TREES_MAX, an unknown kind, item_len == 0, a LIST item_len
+ * above 128, n above its capacity, capacity * item_len overflowing, a level 0
+ * given for a list tree, null or misaligned pointers where the shape needs them
+ * (the leaves for m > 0, the levels for min(D_a, D_b) >= 1), d_idx_out NULL with
+ * max_out > 0, an output range that overlaps an input range of the call (a
+ * tree's levels count from the first stored node to its top) or another output
+ * range, 2^31 or more work items (a work item is a subtree of 2^10 chunks). */
+typedef struct mk_tree_diff {
+    uint32_t kind, item_len;            /* MK_TREE_LIST / _STRUCT / _BYTES; item / record / element length */
+    const void *d_a_items, *d_a_level0, *d_a_levels;
+    const void *d_b_items, *d_b_level0, *d_b_levels;
+    uint64_t n_a, capacity_a, n_b, capacity_b;
+    uint64_t* d_idx_out;                /* max_out slots, 8-B aligned; NULL with max_out == 0 */
+    uint64_t max_out;
+} mk_tree_diff;
+typedef struct mk_diff_report {
+    uint64_t total;                     /* differing indices below min(n_a, n_b) */
+    uint64_t first_index;               /* the smallest; 2^64 - 1: none */
+} mk_diff_report;
+int mk_dev_ssz_trees_diff(mk_call* call, const mk_tree_diff* trees, uint32_t ntrees, void* d_reports, void* stream);
+/* Handle forms, the same for the three kinds: the diff of a's tree against b's,
+ * one launch and one read-back.  Both handles must agree in kind, item length,
+ * record layout and device, else MK_EINVAL; both mutexes are taken in address
+ * order.  idx_out (max_out slots, NULL with max_out == 0) gets the differing
+ * indices ascending; *total their exact number, *n_a and *n_b the two counts.
+ * With *total > max_out the first max_out slots hold some max_out of the
+ * differing indices, still ascending: call again with a larger buffer.  a == b
+ * is MK_OK with *total == 0. */
+int mk_list_tree_diff(mk_call* call, mk_list_tree* a, mk_list_tree* b, uint64_t* idx_out, uint64_t max_out,
+                      uint64_t* total, uint64_t* n_a, uint64_t* n_b);
+int mk_struct_list_tree_diff(mk_call* call, mk_struct_list_tree* a, mk_struct_list_tree* b, uint64_t* idx_out,
+                             uint64_t max_out, uint64_t* total, uint64_t* n_a, uint64_t* n_b);
+int mk_bytes_list_tree_diff(mk_call* call, mk_bytes_list_tree* a, mk_bytes_list_tree* b, uint64_t* idx_out,
+                            uint64_t max_out, uint64_t* total, uint64_t* n_a, uint64_t* n_b);
+/* The same for two sets, which must agree as mk_tree_set_copy requires (else
+ * MK_EINVAL and nothing changes).  Both are flushed first, as root does; ONE
+ * launch covers all the trees and one read-back follows.  reports: count + 1.
+ * Tree i's indices go to idx_out + i * max_out_per_tree, ascending, its report
+ * to reports[i]; the last report describes the container: `total` is the number
+ * of message bytes outside every tree's 32-byte root range that differ,
+ * compared on the host from the sets' own copies, `first_index` the first such
+ * offset.  idx_out may be NULL with max_out_per_tree == 0.  a == b is MK_OK with
+ * every total 0.  The counts are mk_tree_set_count's.  The deposit trie has no
+ * diff. */
+int mk_tree_set_diff(mk_call* call, mk_tree_set* a, mk_tree_set* b, mk_diff_report* reports, uint64_t* idx_out,
+                     uint64_t max_out_per_tree);
+
 /* ---- hashutil.MerkleRoot (merkleRoot.go:12-30) -------------------------- */
 /* Root of the heap o[i] = Hash(o[2i] || o[2i+1]) over leaves
  * o[n+i] = Hash(values[i]); values i = data[offs[i], offs[i+1]).  leaves_out

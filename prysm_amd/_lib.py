@@ -219,6 +219,11 @@ _SIGS = {
     "mk_struct_list_tree_audit": (_int, [_cp, _vp, _vp]),
     "mk_bytes_list_tree_audit": (_int, [_cp, _vp, _vp]),
     "mk_tree_set_audit": (_int, [_cp, _vp, _vp]),
+    "mk_dev_ssz_trees_diff": (_int, [_cp, _vp, _u32, _vp, _vp]),
+    "mk_list_tree_diff": (_int, [_cp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "mk_struct_list_tree_diff": (_int, [_cp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "mk_bytes_list_tree_diff": (_int, [_cp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "mk_tree_set_diff": (_int, [_cp, _vp, _vp, _vp, _vp, _u64]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),
@@ -281,6 +286,21 @@ class AuditReport(ctypes.Structure):
 
     def astuple(self):
         return int(self.bad), int(self.first_level), int(self.first_index)
+
+
+class TreeDiff(ctypes.Structure):
+    """mk_tree_diff: one pair of trees of mk_dev_ssz_trees_diff."""
+    _fields_ = [("kind", _u32), ("item_len", _u32), ("d_a_items", _vp), ("d_a_level0", _vp), ("d_a_levels", _vp),
+                ("d_b_items", _vp), ("d_b_level0", _vp), ("d_b_levels", _vp), ("n_a", _u64), ("capacity_a", _u64),
+                ("n_b", _u64), ("capacity_b", _u64), ("d_idx_out", _vp), ("max_out", _u64)]
+
+
+class DiffReport(ctypes.Structure):
+    """mk_diff_report: the number of differing indices and the smallest (2^64 - 1: none)."""
+    _fields_ = [("total", _u64), ("first_index", _u64)]
+
+    def astuple(self):
+        return int(self.total), int(self.first_index)
 
 
 _lib = None

@@ -11,6 +11,7 @@
 #include "tree_audit.hpp"
 #include "tree_compact.hpp"
 #include "tree_copy.hpp"
+#include "tree_diff.hpp"
 
 namespace mk {
 
@@ -969,6 +970,170 @@ __global__ __launch_bounds__(64) void k_audit_reports(AuditReport* reports, uint
         r.first_level = (uint32_t)(r.key >> kAuditKeyShift);
         r.key &= (1ull << kAuditKeyShift) - 1;
     }
+}
+
+// ----------------------------------------------------------------------------
+// Diff of two resident trees by Merkle descent (the rule:
+// tree_diff.hpp).  A work item is one subtree of height h0 of one pair; a
+// prefix of the pairs' item counts in LDS maps a workgroup's turn to (pair,
+// subtree), the turns by grid stride.  Every thread loads the subtree's root
+// from both trees (the same 2 x 32 bytes: workgroup-uniform); comparable and
+// equal ends the item there, without a barrier.  Otherwise the workgroup walks
+// down with the frontier in LDS, as indices local to the subtree: a lane takes
+// one frontier node, compares it when it is comparable and counts the children
+// that go on (0, 1 or 2); their places come from two wave ballots and one LDS
+// add per wave.  The level-1 nodes that remain name the leaves: a lane per
+// value below m, 2 x 16-B loads for a 32-B entry, for list items 16-B loads
+// where both sides' addresses are equally aligned with byte loads around them,
+// byte loads otherwise.  A wave reserves its slots with one add on the pair's
+// total and lowers first_index with one min; an index is stored only below
+// max_out.  No workgroup waits for another and every loop is bounded by a
+// count computed from n_a and n_b.
+namespace {
+
+__device__ __forceinline__ bool diff_node_ne(const uint8_t* a, const uint8_t* b) {
+    const uint4 a0 = audit_ld16(a), a1 = audit_ld16(a + 16), b0 = audit_ld16(b), b1 = audit_ld16(b + 16);
+    return audit_differs(a0, a1, b0, b1);
+}
+
+// s bytes at pa against s bytes at pb; no byte outside them is read
+__device__ __forceinline__ bool diff_leaf_ne(const uint8_t* pa, const uint8_t* pb, uint32_t s) {
+    uint32_t k = 0, acc = 0;
+    if (((((uintptr_t)pa) ^ ((uintptr_t)pb)) & 15u) == 0) {
+        const uint32_t lead = (16u - (uint32_t)(((uintptr_t)pa) & 15u)) & 15u, head = lead < s ? lead : s;
+        for (; k < head; ++k) acc |= (uint32_t)(pa[k] ^ pb[k]);
+        for (; k + 16u <= s; k += 16u) {
+            const uint4 x = audit_ld16(pa + k), y = audit_ld16(pb + k);
+            acc |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+        }
+    }
+    for (; k < s; ++k) acc |= (uint32_t)(pa[k] ^ pb[k]);
+    return acc != 0;
+}
+
+__device__ __forceinline__ uint32_t diff_lanes_below(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kDiffThreads) void k_trees_diff(TreesDiffArgs g) {
+    __shared__ uint64_t ifirst[kTreesMax + 1];      // the call's first work item of pair t; [ntrees]: the total
+    __shared__ uint32_t front[2][kDiffFrontMax];    // a level's frontier, local to the subtree; then the level-1 nodes
+    __shared__ uint32_t cnt[kDiffHeight + 1];       // nodes in the frontier of level d; [0]: level-1 nodes that remain
+    const uint32_t nt = g.ntrees < kTreesMax ? g.ntrees : kTreesMax;
+    const uint32_t L = threadIdx.x & 63u;
+    if (threadIdx.x == 0) {
+        uint64_t a = 0;
+        for (uint32_t t = 0; t < nt; ++t) {
+            const DiffTree& T = g.t[t];
+            ifirst[t] = a;
+            a += diff_items(diff_shape(T.n_a, T.cap_a, T.n_b, T.cap_b, T.len0));
+        }
+        ifirst[nt] = a;
+    }
+    __syncthreads();
+    const uint64_t total = ifirst[nt];
+    for (uint64_t q = blockIdx.x; q < total; q += gridDim.x) {
+        uint32_t t = 0;
+        while (q >= ifirst[t + 1]) ++t;  // q < ifirst[nt]
+        t = __builtin_amdgcn_readfirstlane(t);  // workgroup-uniform: the descriptor by scalar loads
+        const DiffTree& T = g.t[t];
+        const DiffShape s = diff_shape(T.n_a, T.cap_a, T.n_b, T.cap_b, T.len0);
+        const uint64_t j0 = q - ifirst[t];
+        const uint32_t h0 = s.h0;
+        // the subtree's root: the common case ends here
+        if (h0 >= 1 && diff_comparable(s, h0, j0) &&
+            !diff_node_ne(T.a_levels + 32 * diff_node_a(s, h0, j0), T.b_levels + 32 * diff_node_b(s, h0, j0)))
+            continue;
+        __syncthreads();  // the lists of this workgroup's previous item are free
+        if (threadIdx.x == 0) {
+            for (uint32_t d = 0; d <= kDiffHeight; ++d) cnt[d] = 0;
+            front[0][0] = 0;
+            if (h0 >= 2) {
+                front[0][1] = 1;
+                cnt[h0 - 1] = diff_visited(s, h0 - 1, 2 * j0 + 1) ? 2u : 1u;
+            } else {
+                cnt[0] = 1;  // level-1 node j0, or chunk 0 of a tree without levels
+            }
+        }
+        __syncthreads();
+        uint32_t cur = 0;
+        for (uint32_t d = h0 >= 2 ? h0 - 1 : 0; d >= 1; --d) {
+            const uint32_t F = cnt[d];                 // <= 2^(h0 - d)
+            const uint64_t jbase = j0 << (h0 - d);     // the subtree's first node of level d
+            const uint8_t* la = T.a_levels + 32 * diff_node_a(s, d, jbase);
+            const uint8_t* lb = T.b_levels + 32 * diff_node_b(s, d, jbase);
+            for (uint32_t base = 0; base < F; base += kDiffThreads) {
+                const uint32_t f = base + threadIdx.x;
+                uint32_t local = 0;
+                bool go = false, two = false;
+                if (f < F) {
+                    local = front[cur][f];
+                    const uint64_t j = jbase + local;
+                    go = !diff_comparable(s, d, j) || diff_node_ne(la + 32ull * local, lb + 32ull * local);
+                    two = go && d >= 2 && diff_visited(s, d - 1, 2 * j + 1);
+                }
+                const uint64_t b1 = __ballot(go), b2 = __ballot(two);
+                if (b1 == 0) continue;  // wave-uniform
+                const uint32_t add = (uint32_t)__popcll(b1) + (uint32_t)__popcll(b2);
+                uint32_t at = 0;
+                if (L == 0) at = atomicAdd(&cnt[d - 1], add);  // one LDS add per wave
+                at = __builtin_amdgcn_readfirstlane(at) + diff_lanes_below(b1) + diff_lanes_below(b2);
+                if (go) {
+                    front[cur ^ 1][at] = d >= 2 ? 2 * local : local;
+                    if (two) front[cur ^ 1][at + 1] = 2 * local + 1;
+                }
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        // the leaves under the level-1 nodes that remain: per values each, those below m
+        const uint32_t F = cnt[0], per = 2 * s.p, E = F * per;  // <= 2^9 * 256
+        const uint64_t j1base = h0 >= 1 ? j0 << (h0 - 1) : 0;
+        DiffReport* rep = g.reports + t;
+        for (uint32_t base = 0; base < E; base += kDiffThreads) {
+            const uint32_t e = base + threadIdx.x;
+            bool ne = false;
+            uint64_t i = 0;
+            if (e < E) {
+                const uint32_t f = e / per, v = e - f * per;
+                i = (j1base + front[cur][f]) * per + v;
+                if (i < s.m) {
+                    if (s.len0 == 32u && ((((uintptr_t)T.a_leaves) | ((uintptr_t)T.b_leaves)) & 15u) == 0)
+                        ne = diff_node_ne(T.a_leaves + 32 * i, T.b_leaves + 32 * i);
+                    else
+                        ne = diff_leaf_ne(T.a_leaves + i * s.len0, T.b_leaves + i * s.len0, s.len0);
+                }
+            }
+            const uint64_t bal = __ballot(ne);
+            if (bal == 0) continue;  // wave-uniform
+            const uint32_t leader = (uint32_t)__ffsll((long long)bal) - 1u;
+            uint32_t lo = 0, hi = 0;
+            if (L == leader) {  // one add per wave reserves its slots
+                const uint64_t got = __hip_atomic_fetch_add(&rep->total, (uint64_t)__popcll(bal), __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_AGENT);
+                lo = (uint32_t)got, hi = (uint32_t)(got >> 32);
+            }
+            lo = __builtin_amdgcn_readlane(lo, leader), hi = __builtin_amdgcn_readlane(hi, leader);
+            const uint64_t slot = (((uint64_t)hi << 32) | lo) + diff_lanes_below(bal);
+            if (ne && slot < T.max_out) T.idx_out[slot] = i;
+            uint64_t mn = ne ? i : ~0ull;
+#pragma unroll
+            for (uint32_t o = 32; o >= 1; o >>= 1) {
+                const uint64_t other = __shfl_xor(mn, (int)o);
+                mn = other < mn ? other : mn;
+            }
+            if (L == leader)
+                (void)__hip_atomic_fetch_min(&rep->first_index, mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_diff_reports(DiffReport* reports, uint32_t count) {
+    if (threadIdx.x >= count) return;
+    reports[threadIdx.x].total = 0;
+    reports[threadIdx.x].first_index = ~0ull;
 }
 
 }  // namespace mk

@@ -319,4 +319,32 @@ __global__ void k_audit_compare(const uint4* fresh, const uint4* stored, uint64_
 // first_index) after them
 __global__ void k_audit_reports(AuditReport* reports, uint32_t count, uint32_t finish);
 
+// Diff of up to kTreesMax pairs of resident trees by Merkle descent (tree_diff_api.cpp; the
+// rule: tree_diff.hpp).  The descriptors by value, 1.4 KB of kernel arguments; nothing but the reports and the
+// pairs' index buffers is written.
+struct DiffTree {
+    const uint8_t *a_leaves, *a_levels;  // the leaves: the items of a list tree, else the 32-B roots / digests
+    const uint8_t *b_leaves, *b_levels;
+    uint64_t n_a, cap_a, n_b, cap_b;
+    uint64_t* idx_out;  // max_out slots
+    uint64_t max_out;
+    uint32_t len0;  // bytes of a leaf: 1 .. 128
+    uint32_t pad;
+};
+// mk_diff_report's 16 bytes
+struct DiffReport {
+    uint64_t total;        // differing indices, exact
+    uint64_t first_index;  // the smallest, ~0: none
+};
+struct TreesDiffArgs {
+    DiffTree t[kTreesMax];
+    DiffReport* reports;  // ntrees, cleared before the launch
+    uint32_t ntrees;
+};
+constexpr uint32_t kDiffThreads = 256;
+// one work item (a subtree of height h0 of one pair) per workgroup turn, a bounded grid striding over them
+__global__ void k_trees_diff(TreesDiffArgs g);
+// count reports cleared to (0, ~0)
+__global__ void k_diff_reports(DiffReport* reports, uint32_t count);
+
 }  // namespace mk

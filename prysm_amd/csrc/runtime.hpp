@@ -339,6 +339,18 @@ const StructTreeLayout* struct_tree_layout_of(const TreeHandle& t);
 // one tree's audit: one chain, one read-back
 int tree_audit(TreeHandle* t, mk_audit_report* out);
 
+// ---- the diff of resident trees (tree_diff_api.cpp) ------------------------------
+// mk_dev_ssz_trees_diff: every argument check (no device needed), then the reports cleared and the one launch on st
+int trees_diff_check(const mk_tree_diff* trees, uint32_t ntrees, const void* d_reports);
+int trees_diff_launch(const mk_tree_diff* trees, uint32_t ntrees, void* d_reports, hipStream_t st);
+// the pair (a, b) of two handles as the diff takes it (the caller holds both locks)
+mk_tree_diff tree_diff_desc(const TreeHandle& a, const TreeHandle& b, uint64_t* d_idx_out, uint64_t max_out);
+// the first min(total, max_out) of the max_out slots read back, ascending
+void tree_diff_sort(uint64_t* slots, uint64_t total, uint64_t max_out);
+// two handles' diff: one launch, one read-back
+int tree_diff(TreeHandle* a, TreeHandle* b, uint64_t* idx_out, uint64_t max_out, uint64_t* total, uint64_t* n_a,
+              uint64_t* n_b);
+
 // ---- several trees in one call (tree_many_api.cpp) ------------------------------------------
 // mk_ssz_trees_update_workspace_bytes with its error, and mk_dev_ssz_trees_update
 // after bind_stream(): every check, then the launches on st

@@ -378,4 +378,10 @@ int mk_struct_list_tree_audit(mk_call* call, mk_struct_list_tree* t, mk_audit_re
     return S.done(tree_audit(t, out));
 }
 
+int mk_struct_list_tree_diff(mk_call* call, mk_struct_list_tree* a, mk_struct_list_tree* b, uint64_t* idx_out,
+                             uint64_t max_out, uint64_t* total, uint64_t* n_a, uint64_t* n_b) {
+    Scope S(call);
+    return S.done(tree_diff(a, b, idx_out, max_out, total, n_a, n_b));
+}
+
 }  // extern "C"

@@ -466,4 +466,62 @@ int tree_audit(TreeHandle* t, mk_audit_report* out) {
     return MK_OK;
 }
 
+// ---- diff -------------------------------------------------------------------------
+mk_tree_diff tree_diff_desc(const TreeHandle& a, const TreeHandle& b, uint64_t* d_idx_out, uint64_t max_out) {
+    mk_tree_diff d{};
+    d.kind = a.kind->id;
+    d.item_len = a.item_len;
+    const bool l0 = a.kind->level0;
+    d.d_a_items = a.items.p, d.d_a_level0 = l0 ? a.level0.p : nullptr, d.d_a_levels = a.levels.p;
+    d.d_b_items = b.items.p, d.d_b_level0 = l0 ? b.level0.p : nullptr, d.d_b_levels = b.levels.p;
+    d.n_a = a.count, d.capacity_a = a.cap;
+    d.n_b = b.count, d.capacity_b = b.cap;
+    d.d_idx_out = max_out ? d_idx_out : nullptr;
+    d.max_out = max_out;
+    return d;
+}
+
+void tree_diff_sort(uint64_t* slots, uint64_t total, uint64_t max_out) {
+    std::sort(slots, slots + std::min(total, max_out));
+}
+
+// a's workspace holds the report (its front, 16 bytes) and the max_out slots
+// behind it: one launch, one read-back of both.
+int tree_diff(TreeHandle* a, TreeHandle* b, uint64_t* idx_out, uint64_t max_out, uint64_t* total, uint64_t* n_a,
+              uint64_t* n_b) {
+    if (!a || !b || !total || !n_a || !n_b || (max_out && !idx_out)) return fail(MK_EINVAL, "null pointer");
+    if (max_out >= (1ull << 60)) return fail(MK_EINVAL, "max_out * 8 overflows");
+    if (a == b) {
+        std::lock_guard<std::mutex> tl(a->mu);
+        *total = 0;
+        *n_a = *n_b = a->count;
+        return MK_OK;
+    }
+    // both handles' mutexes, the one at the lower address first (as tree_copy)
+    std::mutex *first = &a->mu, *second = &b->mu;
+    if (std::less<std::mutex*>()(second, first)) std::swap(first, second);
+    std::lock_guard<std::mutex> l1(*first);
+    std::lock_guard<std::mutex> l2(*second);
+    if (!tree_same_shape(*a, *b))
+        return fail(MK_EINVAL, "a diff between a %s of %u-byte %s and a %s of %u-byte %s, or of another layout",
+                    a->kind->name, a->item_len, a->kind->noun, b->kind->name, b->item_len, b->kind->noun);
+    if (a->dev != b->dev) return fail(MK_EINVAL, "the trees live on devices %d and %d", a->dev, b->dev);
+    TRY(bind_dev(a->dev));
+    hipStream_t st = ctx()->stream;
+    TRY(grow(a->ws, 16 + 8 * max_out));
+    uint8_t* ws = (uint8_t*)a->ws.p;
+    const mk_tree_diff d = tree_diff_desc(*a, *b, (uint64_t*)(ws + 16), max_out);
+    TRY(trees_diff_check(&d, 1, ws));
+    TRY(trees_diff_launch(&d, 1, ws, st));
+    std::vector<uint64_t> back(2 + max_out);
+    HIPCHK(hipMemcpyAsync(back.data(), ws, 8 * back.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *total = back[0];
+    *n_a = a->count;
+    *n_b = b->count;
+    tree_diff_sort(back.data() + 2, back[0], max_out);
+    if (max_out) std::memcpy(idx_out, back.data() + 2, 8 * std::min(back[0], max_out));
+    return MK_OK;
+}
+
 }  // namespace mk::rt

@@ -458,10 +458,9 @@ int set_clone(mk_tree_set* src, mk_tree_set** out) {
     return MK_OK;
 }
 
-int set_copy(mk_tree_set* dst, mk_tree_set* src) {
-    if (!dst || !src) return fail(MK_EINVAL, "null pointer");
-    if (dst == src) return MK_OK;
-    LockBoth lk(dst->mu, src->mu);
+// what a copy and a diff ask of two sets (both locked): the same container length, device and, tree by tree,
+// kind, item length, record layout and container offset
+int sets_agree(const mk_tree_set* dst, const mk_tree_set* src) {
     if (dst->container_len != src->container_len)
         return fail(MK_EINVAL, "containers of %u and %u bytes", dst->container_len, src->container_len);
     if (dst->trees.size() != src->trees.size())
@@ -473,6 +472,14 @@ int set_copy(mk_tree_set* dst, mk_tree_set* src) {
     }
     if (!src->trees.empty() && dst->dev != src->dev)
         return fail(MK_EINVAL, "the sets live on devices %d and %d", dst->dev, src->dev);
+    return MK_OK;
+}
+
+int set_copy(mk_tree_set* dst, mk_tree_set* src) {
+    if (!dst || !src) return fail(MK_EINVAL, "null pointer");
+    if (dst == src) return MK_OK;
+    LockBoth lk(dst->mu, src->mu);
+    TRY(sets_agree(dst, src));
     TRY(settle(src));
     if (!src->trees.empty()) TRY(bind_set(src));
     return copy_trees(dst, src);
@@ -521,9 +528,66 @@ int set_audit(mk_tree_set* s, mk_audit_report* out) {
     return MK_OK;
 }
 
+// ---- diff -------------------------------------------------------------------------
+// Both sets flushed and waited for, as for a root; then the one launch of
+// tree_diff_api.cpp over all the pairs and one read-back.  a's workspace holds
+// the reports (its front, 256 bytes) and the trees' slots behind them.  The
+// container's report is the host's: the two messages outside the trees' roots.
+int set_diff(mk_tree_set* a, mk_tree_set* b, mk_diff_report* reports, uint64_t* idx_out, uint64_t per) {
+    if (!a || !b || !reports || (per && !idx_out)) return fail(MK_EINVAL, "null pointer");
+    if (per >= (1ull << 56)) return fail(MK_EINVAL, "max_out_per_tree * 8 * %d overflows", MK_TREES_MAX);
+    if (a == b) {
+        std::lock_guard<std::mutex> lk(a->mu);
+        for (size_t i = 0; i <= a->trees.size(); ++i) reports[i] = mk_diff_report{0, ~0ull};
+        return MK_OK;
+    }
+    LockBoth lk(a->mu, b->mu);
+    TRY(sets_agree(a, b));
+    const uint32_t nt = (uint32_t)a->trees.size();
+    TRY(settle(a));
+    TRY(settle(b));
+    for (uint32_t i = 0; i <= nt; ++i) reports[i] = mk_diff_report{0, ~0ull};
+    if (nt) {
+        TRY(bind_set(a));
+        hipStream_t st = ctx()->stream;
+        static_assert(MK_TREES_MAX * sizeof(mk_diff_report) <= 256, "the reports' room at the workspace's front");
+        TRY(grow(a->ws, 256 + 8 * per * nt));
+        uint8_t* ws = (uint8_t*)a->ws.p;
+        mk_tree_diff table[MK_TREES_MAX] = {};
+        for (uint32_t i = 0; i < nt; ++i)
+            table[i] = tree_diff_desc(*a->trees[i].h, *b->trees[i].h, (uint64_t*)(ws + 256) + per * i, per);
+        TRY(trees_diff_check(table, nt, ws));
+        TRY(trees_diff_launch(table, nt, ws, st));
+        std::vector<uint64_t> back(32 + per * nt);
+        HIPCHK(hipMemcpyAsync(back.data(), ws, 8 * back.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint32_t i = 0; i < nt; ++i) {
+            reports[i] = mk_diff_report{back[2 * i], back[2 * i + 1]};
+            uint64_t* slots = back.data() + 32 + per * i;
+            tree_diff_sort(slots, reports[i].total, per);
+            if (per) std::memcpy(idx_out + per * i, slots, 8 * std::min(reports[i].total, per));
+        }
+    }
+    // the message outside every tree's root: what put() wrote
+    std::vector<uint8_t> skip(a->container_len, 0);
+    for (const auto& t : a->trees)
+        if (t.coff != MK_NO_CONTAINER) std::fill(skip.begin() + t.coff, skip.begin() + t.coff + 32, 1);
+    for (uint32_t o = 0; o < a->container_len; ++o) {
+        if (skip[o] || a->msg[o] == b->msg[o]) continue;
+        if (reports[nt].total++ == 0) reports[nt].first_index = o;
+    }
+    return MK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mk_tree_set_diff(mk_call* call, mk_tree_set* a, mk_tree_set* b, mk_diff_report* reports, uint64_t* idx_out,
+                     uint64_t max_out_per_tree) {
+    Scope S(call);
+    return S.done(set_diff(a, b, reports, idx_out, max_out_per_tree));
+}
 
 int mk_tree_set_audit(mk_call* call, mk_tree_set* s, mk_audit_report* out) {
     Scope S(call);

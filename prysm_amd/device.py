@@ -1026,6 +1026,76 @@ def audit_reports(reports: torch.Tensor):
     return out
 
 
+class TreeDiffArgs:
+    """One pair of ``trees_diff`` (mk_tree_diff): two built trees of ``kind`` and
+    ``item_len``, ``n_a`` values laid out for ``capacity_a`` against ``n_b`` for
+    ``capacity_b``.  ``*_level0``: the struct roots / element digests of a
+    STRUCT / BYTES tree (None for a list tree; its ``*_items`` are not read).
+    ``idx_out``: a uint64 device tensor whose ``max_out`` (default: all) slots
+    take the differing indices; None with ``max_out`` 0."""
+
+    def __init__(self, kind: int, item_len: int, a_items: torch.Tensor, a_levels: torch.Tensor, n_a: int,
+                 capacity_a: int, b_items: torch.Tensor, b_levels: torch.Tensor, n_b: int, capacity_b: int,
+                 idx_out: torch.Tensor = None, max_out: int = None, a_level0: torch.Tensor = None,
+                 b_level0: torch.Tensor = None):
+        self.kind, self.item_len = kind, item_len
+        self.a = (a_items, a_level0, a_levels, n_a, capacity_a)
+        self.b = (b_items, b_level0, b_levels, n_b, capacity_b)
+        self.idx_out = idx_out
+        self.max_out = (idx_out.numel() if idx_out is not None else 0) if max_out is None else max_out
+
+
+def trees_diff(trees, reports: torch.Tensor = None, stream=None) -> torch.Tensor:
+    """Diff up to 16 pairs of built resident trees (``TreeDiffArgs``) by Merkle
+    descent, read-only, in one launch on ``stream`` (default: the current one;
+    mk_dev_ssz_trees_diff).  Pair i's differing indices below
+    min(n_a, n_b) go to its ``idx_out`` in no particular order, only into slots
+    below ``max_out``.  Returns ``reports``, a device tensor of 16 * len(trees)
+    bytes -- (total, first_index) per pair, ``total`` exact; ``diff_reports``
+    turns it into tuples.  Nothing is allocated when ``reports`` is given: the
+    call can be captured."""
+    if not trees:
+        raise ValueError("no trees")
+    arr = (_lib.TreeDiff * len(trees))()
+    some = None
+    for d, t in zip(arr, trees):
+        leaf = t.item_len if t.kind == _lib.MK_TREE_LIST else 32
+        d.kind, d.item_len = t.kind, t.item_len
+        for side, (items, level0, levels, n, cap) in (("a", t.a), ("b", t.b)):
+            if items is not None and items.numel() * items.element_size() < n * t.item_len:
+                raise ValueError("value buffer shorter than n * item_len")
+            if level0 is not None and level0.numel() * level0.element_size() < 32 * n:
+                raise ValueError("level-0 buffer shorter than 32 * n")
+            if levels is not None and levels.numel() * levels.element_size() < list_tree_levels_bytes(cap, leaf):
+                raise ValueError("level buffer smaller than mk_ssz_list_tree_levels_bytes(capacity, leaf length)")
+            for name, x in (("items", items), ("level0", level0), ("levels", levels)):
+                setattr(d, f"d_{side}_{name}", x.data_ptr() if x is not None else None)
+                some = x if some is None and x is not None else some
+            setattr(d, f"n_{side}", n)
+            setattr(d, f"capacity_{side}", cap)
+        if t.idx_out is not None and (t.idx_out.element_size() != 8 or t.idx_out.is_floating_point()):
+            raise ValueError("idx_out must be a 64-bit integer tensor")
+        if t.max_out and (t.idx_out is None or t.idx_out.numel() < t.max_out):
+            raise ValueError("idx_out shorter than max_out")
+        d.d_idx_out = t.idx_out.data_ptr() if t.idx_out is not None and t.max_out else None
+        d.max_out = t.max_out
+    if reports is None:
+        if some is None:
+            raise ValueError("no device buffer to take the device from: pass reports")
+        reports = torch.empty(16 * len(trees), dtype=torch.uint8, device=some.device)
+    if reports.numel() * reports.element_size() < 16 * len(trees):
+        raise ValueError("reports shorter than 16 * len(trees) bytes")
+    st = _stream(reports.device) if stream is None else ctypes.c_void_p(getattr(stream, "cuda_stream", stream))
+    _lib.invoke("mk_dev_ssz_trees_diff", arr, len(trees), _p(reports), st, device=_dev(reports))
+    return reports
+
+
+def diff_reports(reports: torch.Tensor):
+    """``trees_diff``'s device reports as host tuples ``(total, first_index)`` (synchronises)."""
+    raw = np.ascontiguousarray(reports.cpu().numpy()).view(np.uint8).reshape(-1, 16)
+    return [tuple(int(x) for x in r.copy().view(np.uint64)) for r in raw]
+
+
 def prof_enable(on: bool = True) -> None:
     _lib.check(_lib.load().mk_prof_enable(int(on)), "mk_prof_enable")
 

@@ -44,6 +44,8 @@ import numpy as np
 from . import _lib
 from .hashutil import _ptr
 
+DIFF_FIRST = 4096  # index slots of a diff()'s first call when the caller sets no bound
+
 
 class _Tree:
     """What the three handles share: a list of ``_len``-byte values behind the
@@ -191,6 +193,31 @@ class _Tree:
         out = _lib.AuditReport()
         self._call("audit", ctypes.byref(out))
         return out.astuple()
+
+    def diff(self, other, max_out: int = None):
+        """Which values differ between this tree and ``other`` (the same kind,
+        value length and layout, else it raises)?  Found in HBM by walking
+        down from the top only through stored nodes that differ (DESIGN.md
+        §5o): ``(indices, total, n_self, n_other)`` -- the differing indices
+        below min(n_self, n_other) as an ascending uint64 array, their exact
+        number and the two counts.  A StructListTree compares the records'
+        roots, a BytesListTree the elements' digests.  With ``max_out`` the
+        array holds at most that many of them (``total`` says how many there
+        are); None: all of them, with a second call when there are more than
+        ``DIFF_FIRST``.  One launch and one read-back per call."""
+        if type(other) is not type(self):
+            raise _lib.MerkleError(_lib.MK_EINVAL, f"diff: a {type(other).__name__} against a {type(self).__name__}")
+        want = DIFF_FIRST if max_out is None else int(max_out)
+        while True:
+            out = np.empty(want, dtype=np.uint64)
+            total, na, nb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            self._call("diff", other._handle, _ptr(out) if want else None, want, ctypes.byref(total), ctypes.byref(na),
+                       ctypes.byref(nb))
+            if max_out is None and total.value > want:
+                want = int(total.value)
+                max_out = want  # once: the trees may change between the two calls
+                continue
+            return out[:min(total.value, want)].copy(), int(total.value), int(na.value), int(nb.value)
 
 
 def verify_branches(values, indices, n: int, item_len: int, branches, root, container=None,
@@ -449,6 +476,36 @@ class TreeSet:
         out = (_lib.AuditReport * (len(self) + 1))()
         self._call("audit", out)
         return [r.astuple() for r in out]
+
+    def diff(self, other, max_out: int = None):
+        """Which values differ between this set and ``other`` (sets that agree as
+        ``copy_from`` requires, else it raises and nothing changes)?  Both are
+        flushed first, as ``root()`` does; one launch walks all the trees down
+        from their tops through the stored nodes that differ
+        and one read-back follows.  A dict: tree number -> ``(indices, total,
+        n_self, n_other)`` as ``_Tree.diff``, and ``"container"`` -> ``(total,
+        first_offset)``, the bytes of the two messages outside every tree's
+        root that differ (what ``put`` wrote) and the first such offset (None:
+        none).  ``max_out`` bounds the indices per tree; None: all of them,
+        with a second call when a tree has more than ``DIFF_FIRST``."""
+        nt = len(self)
+        per = DIFF_FIRST if max_out is None else int(max_out)
+        while True:
+            reports = (_lib.DiffReport * (nt + 1))()
+            out = np.empty((nt, per), dtype=np.uint64)
+            self._call("diff", other._handle, reports, _ptr(out) if out.size else None, per)
+            most = max((int(r.total) for r in reports[:nt]), default=0)
+            if max_out is None and most > per:
+                per = max_out = most  # once
+                continue
+            break
+        res = {}
+        for i in range(nt):
+            total = int(reports[i].total)
+            res[i] = (out[i, :min(total, per)].copy(), total, self.count(i), other.count(i))
+        total, first = reports[nt].astuple()
+        res["container"] = (total, first if total else None)
+        return res
 
     def leaf_len(self, tree) -> int:
         """Bytes of a level-0 entry of a tree: what ``branches`` proves."""
