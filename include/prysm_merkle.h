@@ -980,8 +980,8 @@ int mk_dev_ssz_trees_audit(mk_call* call, const mk_tree_audit* trees, uint32_t n
 /* Handle forms: the audit of the handle's tree, one read-back of its report
  * (*out).  mk_tree_set_audit flushes what is pending, as root does, then audits
  * all the trees and the message in the same launch: out gets count + 1 reports,
- * the container's last; a set without trees is MK_EINVAL.  The deposit trie has
- * no audit. */
+ * the container's last; a set without trees is MK_EINVAL.  The deposit trie's
+ * audit is mk_deposit_trie_audit, with the same report. */
 int mk_list_tree_audit(mk_call* call, mk_list_tree* t, mk_audit_report* out);
 int mk_struct_list_tree_audit(mk_call* call, mk_struct_list_tree* t, mk_audit_report* out);
 int mk_bytes_list_tree_audit(mk_call* call, mk_bytes_list_tree* t, mk_audit_report* out);
@@ -1211,6 +1211,66 @@ int mk_deposit_trie_branches(mk_call* call, mk_trie* t, uint64_t as_of, const ui
 int mk_deposit_trie_root_at(mk_call* call, mk_trie* t, uint64_t as_of, uint8_t root[32]);
 /* Leaf hashes [first, first + cnt) (Hash(deposit)), cnt x 32 bytes. */
 int mk_deposit_trie_leaves(mk_call* call, mk_trie* t, uint64_t first, uint64_t cnt, uint8_t* out);
+
+/* ---- the resident deposit trie rolled back, compared, audited, copied ---- */
+/* cnt(c, d) = ceil(c / 2^d) nodes of level d are LIVE in a trie of c deposits;
+ * a node at or beyond that is dead: no entry point of this library reads one.
+ * truncate: the trie of the first new_count <= count deposits, without the
+ *   deposit data: per level d = 1 .. depth at most one node, (new_count - 1) >>
+ *   d, covers deposits on both sides of new_count; it gets the value it had
+ *   after the new_count-th append, one chain of at most `depth` hashes from the
+ *   stored nodes (the as-of rule of mk_dev_deposit_trie_branches).  Nothing else
+ *   of the level array is written, dead nodes keep their bytes; the root goes
+ *   to d_root32 (0^32 for new_count == 0, when level `depth` node 0 is zeroed
+ *   too).  new_count == count writes only the root.  One single-wave launch.
+ *   ETH1 reorganisations (types.Log.Removed): roll back to the removed log's
+ *   deposit index, then append again.
+ * fork_point: the smallest leaf index i < m = min(count_a, count_b) at which
+ *   the two tries' level-0 nodes differ, m when none does, as one uint64 to
+ *   d_out8.  Both tries have depth `depth`; counts and capacities may differ.
+ *   Only nodes whose leaves all lie below m are compared; nothing is hashed.
+ *   One single-wave launch.
+ * audit: for d = 1 .. depth and j < cnt(count, d), stored node (d, j) against
+ *   K(level_{d-1}[2j] || R), R = level_{d-1}[2j+1] when 2j+1 < cnt(count, d-1),
+ *   else 0^32; d_root32 against level `depth` node 0 (0^32 for count == 0).
+ *   The report is mk_audit_report: keys (level, index), levels 1 .. depth and
+ *   MK_AUDIT_ROOT; level 0 is never reported (no deposit data is kept).  A wrong
+ *   interior node is reported where it is stored and one level up.  More than
+ *   2^31 work items is MK_EINVAL.  Three launches in a chain: the report
+ *   cleared, every node in one launch, the key unpacked.
+ * copy: the live nodes of level 0 .. depth from the layout of src_capacity to
+ *   that of dst_capacity >= count, and the root (both root pointers NULL: no
+ *   root travels).  The buffers must not overlap.  One launch.
+ * All four: d_levels and roots 16-B aligned, d_report and d_out8 8-B aligned.
+ * MK_EINVAL, every check before a device is looked up and nothing launched:
+ * new_count > count, count > capacity, a count above 2^depth, depth outside
+ * 1..63, a null or misaligned pointer, overlapping copy buffers.  They allocate
+ * nothing, upload nothing, never synchronise and can be captured into a
+ * hipGraph (a linear chain of nodes). */
+int mk_dev_deposit_trie_truncate(mk_call* call, void* d_levels, uint64_t capacity, uint64_t count, uint64_t new_count,
+                                 uint32_t depth, void* d_root32, void* stream);
+int mk_dev_deposit_trie_fork_point(mk_call* call, const void* d_levels_a, uint64_t capacity_a, uint64_t count_a,
+                                   const void* d_levels_b, uint64_t capacity_b, uint64_t count_b, uint32_t depth,
+                                   void* d_out8, void* stream);
+int mk_dev_deposit_trie_audit(mk_call* call, const void* d_levels, uint64_t capacity, uint64_t count, uint32_t depth,
+                              const void* d_root32, void* d_report, void* stream);
+int mk_dev_deposit_trie_copy(mk_call* call, const void* d_src_levels, uint64_t src_capacity, uint64_t count,
+                             void* d_dst_levels, uint64_t dst_capacity, uint32_t depth, const void* d_src_root32,
+                             void* d_dst_root32, void* stream);
+/* Handle forms, one synchronise each.  truncate: the first n deposits stay
+ * (n > count: MK_EINVAL, nothing changes).  fork_point(a, a) is the count.
+ * clone: a new handle of src's depth and capacity on its device, no hashing.
+ * copy: dst becomes src; dst grows to src's capacity only if src's count
+ * does not fit.  reserve: room for `capacity` deposits (never shrinks).  Tries
+ * of different depth or on different devices are MK_EINVAL; two handles are
+ * locked in address order. */
+int mk_deposit_trie_truncate(mk_call* call, mk_trie* t, uint64_t n);
+int mk_deposit_trie_fork_point(mk_call* call, mk_trie* a, mk_trie* b, uint64_t* out);
+int mk_deposit_trie_audit(mk_call* call, mk_trie* t, mk_audit_report* out);
+int mk_deposit_trie_clone(mk_call* call, mk_trie* src, mk_trie** out);
+int mk_deposit_trie_copy(mk_call* call, mk_trie* dst, mk_trie* src);
+int mk_deposit_trie_reserve(mk_call* call, mk_trie* t, uint64_t capacity);
+uint64_t mk_deposit_trie_capacity(const mk_trie* t);
 
 /* Batched VerifyMerkleBranch: ok[i] = fold(leaves[i], branches[i*depth..],
  * indices[i] + 2^tree_depth) == roots[i]. */

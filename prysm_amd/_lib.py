@@ -114,6 +114,17 @@ _SIGS = {
     "mk_dev_deposit_trie_branches": (_int, [_cp, _vp, _u64, _u64, _u32, _u64, _vp, _u64, _vp, _vp, _vp]),
     "mk_deposit_trie_branches": (_int, [_cp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "mk_deposit_trie_root_at": (_int, [_cp, _vp, _u64, _vp]),
+    "mk_dev_deposit_trie_truncate": (_int, [_cp, _vp, _u64, _u64, _u64, _u32, _vp, _vp]),
+    "mk_dev_deposit_trie_fork_point": (_int, [_cp, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "mk_dev_deposit_trie_audit": (_int, [_cp, _vp, _u64, _u64, _u32, _vp, _vp, _vp]),
+    "mk_dev_deposit_trie_copy": (_int, [_cp, _vp, _u64, _u64, _vp, _u64, _u32, _vp, _vp, _vp]),
+    "mk_deposit_trie_truncate": (_int, [_cp, _vp, _u64]),
+    "mk_deposit_trie_fork_point": (_int, [_cp, _vp, _vp, _vp]),
+    "mk_deposit_trie_audit": (_int, [_cp, _vp, _vp]),
+    "mk_deposit_trie_clone": (_int, [_cp, _vp, _vp]),
+    "mk_deposit_trie_copy": (_int, [_cp, _vp, _vp]),
+    "mk_deposit_trie_reserve": (_int, [_cp, _vp, _u64]),
+    "mk_deposit_trie_capacity": (_u64, [_vp]),
     "mk_dev_verify_deposits": (_int, [_cp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32, _vp, _vp]),
     "mk_verify_deposits": (_int, [_cp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32, _vp]),
     "mk_ssz_list_tree_levels_bytes": (_u64, [_u64, _u32]),

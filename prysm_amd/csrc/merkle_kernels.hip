@@ -4140,3 +4140,5 @@ __global__ __launch_bounds__(256) void k_many_final(const uint8_t* __restrict__ 
 // the resident trees: a file of their own, built in this translation unit ("Kernel files")
 #define MK_KERNEL_UNIT 1
 #include "kernels_tree.hip"
+// the deposit trie's roll back, fork point, audit and copy; after kernels_tree.hip: its audit helpers
+#include "kernels_trie_admin.hip"

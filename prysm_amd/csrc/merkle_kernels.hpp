@@ -347,4 +347,19 @@ __global__ void k_trees_diff(TreesDiffArgs g);
 // count reports cleared to (0, ~0)
 __global__ void k_diff_reports(DiffReport* reports, uint32_t count);
 
+// The resident deposit trie rolled back, compared, audited and copied (kernels_trie_admin.hip,
+// trie_admin_api.cpp; the rules: trie_admin.hpp).
+// one wave: the straddling nodes of a roll back to c <= count stored along the as-of chain, the root to root_out
+__global__ void k_trie_truncate(uint4* levels, uint64_t cap, uint64_t count, uint64_t c, uint32_t depth,
+                                uint4* root_out);
+// one wave: the smallest leaf index below min(count_a, count_b) at which the tries differ, else that minimum
+__global__ void k_trie_fork_point(const uint4* a, uint64_t cap_a, uint64_t count_a, const uint4* b, uint64_t cap_b,
+                                  uint64_t count_b, uint32_t depth, uint64_t* out);
+// a bounded grid of kAuditThreads striding over the live nodes of level 1 .. depth and the root
+__global__ void k_trie_audit(const uint4* levels, uint64_t cap, uint64_t count, uint32_t depth, const uint4* root,
+                             AuditReport* report);
+// a bounded grid of kCopyThreads striding over the 16-byte halves of the live nodes (and the root's, when given)
+__global__ void k_trie_copy(const uint4* src, uint64_t cap_src, uint64_t count, uint4* dst, uint64_t cap_dst,
+                            uint32_t depth, const uint4* src_root, uint4* dst_root);
+
 }  // namespace mk

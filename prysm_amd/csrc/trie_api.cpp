@@ -2,18 +2,10 @@
 // the pipelined stream of tries, the mk_trie handle and the mk_*deposit_trie*,
 // mk_*merkle_root* and mk_verify_* entry points.
 #include "runtime.hpp"
+#include "trie_handle.hpp"
 
 using namespace mk;
 using namespace mk::rt;
-
-// ---- deposit trie handle -----------------------------------------------------------------
-struct mk_trie {
-    std::mutex mu;
-    int dev = 0;
-    uint32_t depth = 32;
-    uint64_t cap = 0, count = 0;
-    DevBuf levels, root, in, offs, branch;
-};
 
 namespace {
 

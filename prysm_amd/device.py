@@ -508,6 +508,67 @@ def deposit_trie_branches(levels: torch.Tensor, capacity: int, count: int, depth
     return out
 
 
+def _trie_fits(levels: torch.Tensor, capacity: int, depth: int) -> None:
+    if capacity and 0 < depth < 64 and levels.numel() * levels.element_size() < deposit_trie_levels_bytes(capacity, depth):
+        raise ValueError("level buffer smaller than mk_deposit_trie_levels_bytes(capacity, depth)")
+
+
+def deposit_trie_truncate(levels: torch.Tensor, capacity: int, count: int, new_count: int, depth: int,
+                          root: torch.Tensor) -> None:
+    """Roll the device trie of ``count`` deposits back to its first
+    ``new_count``: one single-wave launch stores the at most ``depth`` nodes
+    that straddle ``new_count`` and the root; nothing else of ``levels`` is
+    written (mk_dev_deposit_trie_truncate)."""
+    _trie_fits(levels, capacity, depth)
+    _lib.invoke("mk_dev_deposit_trie_truncate", _p(levels), capacity, count, new_count, depth, _p(root),
+                _stream(levels.device), device=_dev(levels))
+
+
+def deposit_trie_fork_point(levels_a: torch.Tensor, capacity_a: int, count_a: int, levels_b: torch.Tensor,
+                            capacity_b: int, count_b: int, depth: int, out: torch.Tensor = None) -> torch.Tensor:
+    """The smallest leaf index below min(count_a, count_b) at which two device
+    tries of one depth differ, that minimum when none does: one int64 on the
+    device (mk_dev_deposit_trie_fork_point)."""
+    _trie_fits(levels_a, capacity_a, depth)
+    _trie_fits(levels_b, capacity_b, depth)
+    if out is None:
+        out = torch.empty(1, dtype=torch.int64, device=levels_a.device)
+    elif out.numel() * out.element_size() < 8:
+        raise ValueError("out shorter than 8 bytes")
+    _lib.invoke("mk_dev_deposit_trie_fork_point", _p(levels_a), capacity_a, count_a, _p(levels_b), capacity_b,
+                count_b, depth, _p(out), _stream(levels_a.device), device=_dev(levels_a))
+    return out
+
+
+def deposit_trie_audit(levels: torch.Tensor, capacity: int, count: int, depth: int, root: torch.Tensor,
+                       report: torch.Tensor = None) -> torch.Tensor:
+    """Every stored node of level 1 .. depth of a device trie against the
+    level below it, and ``root`` against the top node, read-only
+    (mk_dev_deposit_trie_audit).  Returns ``report``, 24 bytes on the device:
+    one mk_audit_report; ``audit_reports`` turns it into a tuple."""
+    _trie_fits(levels, capacity, depth)
+    if report is None:
+        report = torch.empty(24, dtype=torch.uint8, device=levels.device)
+    elif report.numel() * report.element_size() < 24:
+        raise ValueError("report shorter than 24 bytes")
+    _lib.invoke("mk_dev_deposit_trie_audit", _p(levels), capacity, count, depth, _p(root), _p(report),
+                _stream(levels.device), device=_dev(levels))
+    return report
+
+
+def deposit_trie_copy(src_levels: torch.Tensor, src_capacity: int, count: int, dst_levels: torch.Tensor,
+                      dst_capacity: int, depth: int, src_root: torch.Tensor = None,
+                      dst_root: torch.Tensor = None) -> None:
+    """The live nodes of a device trie from the layout of ``src_capacity``
+    into that of ``dst_capacity`` >= count, and the root when both root
+    tensors are given: one launch, no hashing (mk_dev_deposit_trie_copy)."""
+    _trie_fits(src_levels, src_capacity, depth)
+    _trie_fits(dst_levels, dst_capacity, depth)
+    _lib.invoke("mk_dev_deposit_trie_copy", _p(src_levels), src_capacity, count, _p(dst_levels), dst_capacity, depth,
+                _p(src_root) if src_root is not None else None, _p(dst_root) if dst_root is not None else None,
+                _stream(src_levels.device), device=_dev(src_levels))
+
+
 def verify_deposits(data: torch.Tensor, offs: torch.Tensor, branches: torch.Tensor, indices: torch.Tensor, n: int,
                     depth: int, roots: torch.Tensor, root_stride: int = 0, tree_depth: int = 32,
                     out: torch.Tensor = None) -> torch.Tensor:

@@ -215,6 +215,101 @@ class DepositTrie:
         _lib.invoke("mk_deposit_trie_leaves", self._handle, index, 1, out, device=self._device)
         return out.raw
 
+    # ---- roll back, fork point, audit, clone / copy / reserve ----
+    def _ensure_handle(self):
+        if self._handle is None:
+            h = ctypes.c_void_p()
+            _lib.invoke("mk_deposit_trie_new", self.depth, self._capacity, ctypes.byref(h), device=self._device)
+            self._handle = h
+        return self._handle
+
+    def truncate(self, n: int) -> None:
+        """Roll back to the first ``n`` deposits (an ETH1 reorganisation: the
+        deposit index of the first removed log).  No deposit data is needed:
+        the at most ``depth`` nodes that straddle ``n`` are recomputed from the
+        stored ones in one launch.  ``n`` beyond the count raises and nothing
+        changes."""
+        self._flush()
+        if not 0 <= n <= self.deposit_count:
+            raise _lib.MerkleError(_lib.MK_EINVAL, f"truncate to {n} outside 0..{self.deposit_count} deposits")
+        if self._handle is not None:
+            _lib.invoke("mk_deposit_trie_truncate", self._handle, n, device=self._device)
+        self.deposit_count = n
+
+    Rollback = truncate
+
+    def fork_point(self, other: "DepositTrie") -> int:
+        """The smallest deposit index at which this trie and ``other`` hold
+        different leaves, min of the two counts when none does."""
+        self._flush()
+        other._flush()
+        if other.depth != self.depth:
+            raise _lib.MerkleError(_lib.MK_EINVAL, f"fork_point: tries of depth {self.depth} and {other.depth}")
+        if self._handle is None or other._handle is None:
+            return 0
+        out = ctypes.c_uint64()
+        _lib.invoke("mk_deposit_trie_fork_point", self._handle, other._handle, ctypes.byref(out),
+                    device=self._device)
+        return int(out.value)
+
+    ForkPoint = fork_point
+
+    def audit(self):
+        """Check every stored node of level 1 .. depth against the level below
+        it and the root against the top node, on the device, read-only:
+        ``(bad, first_level, first_index)`` as the list trees' ``audit()``;
+        ``(0, _lib.MK_AUDIT_NONE, 2**64 - 1)`` for a sound trie.  Level 0 is
+        not checked: the trie keeps no deposit data."""
+        self._flush()
+        if self._handle is None:
+            return 0, _lib.MK_AUDIT_NONE, 2**64 - 1
+        out = _lib.AuditReport()
+        _lib.invoke("mk_deposit_trie_audit", self._handle, ctypes.byref(out), device=self._device)
+        return out.astuple()
+
+    Audit = audit
+
+    def clone(self) -> "DepositTrie":
+        """A new trie holding the same deposits: one copy launch in HBM, no
+        hashing.  The two share nothing afterwards (a candidate ETH1 view)."""
+        self._flush()
+        t = DepositTrie(self.depth, self._capacity, self._device)
+        t.deposit_count = self.deposit_count
+        if self._handle is not None:
+            h = ctypes.c_void_p()
+            _lib.invoke("mk_deposit_trie_clone", self._handle, ctypes.byref(h), device=self._device)
+            t._handle = h
+        return t
+
+    Clone = clone
+
+    def copy_from(self, other: "DepositTrie") -> None:
+        """Make this trie a copy of ``other`` (the same depth, else it raises
+        and nothing changes); it grows only when ``other``'s deposits do not fit."""
+        if other is self:
+            return
+        other._flush()
+        if other.depth != self.depth:
+            raise _lib.MerkleError(_lib.MK_EINVAL, f"copy_from: tries of depth {self.depth} and {other.depth}")
+        self._queue = []
+        if other._handle is None:
+            if self._handle is not None:
+                _lib.invoke("mk_deposit_trie_truncate", self._handle, 0, device=self._device)
+        else:
+            _lib.invoke("mk_deposit_trie_copy", self._ensure_handle(), other._handle, device=self._device)
+        self.deposit_count = other.deposit_count
+
+    def reserve(self, capacity: int) -> None:
+        """Room for ``capacity`` deposits: the next appends up to it move nothing."""
+        self._flush()
+        _lib.invoke("mk_deposit_trie_reserve", self._ensure_handle(), int(capacity), device=self._device)
+
+    @property
+    def capacity(self) -> int:
+        """Deposits the trie has room for before an append moves it."""
+        self._flush()
+        return int(_lib.load().mk_deposit_trie_capacity(self._handle)) if self._handle is not None else 0
+
 
 def verify_merkle_branches(leaves: Sequence[bytes], branches: Sequence[Sequence[bytes]], depth: int,
                            indices: Sequence[int], roots: Sequence[bytes],
