@@ -440,6 +440,38 @@ int mk_dev_ssz_merkle_hash_multi(mk_call* call, const void* const* d_shards, uin
  * root-to-leaf nesting path may sum to at most 320 bytes (each rounded up to
  * 4), otherwise the layout is MK_EINVAL; their records must be 4-byte aligned.
  *
+ * MK_FIELD_LIST: a slice ([]T) of fixed-size items in a slot at a 4-byte
+ * aligned offset: le32(count), then len (the capacity, >= 1) item cells of
+ * `stride` bytes each; the cells beyond count are ignored.  The entry {LIST,
+ * offset, cap} is followed by exactly one item descriptor whose offset member
+ * carries the stride:
+ *   {MK_FIELD_RAW, stride, len}    len 1/2/4/8 and stride == len; the element
+ *                                  hash is the raw encoding
+ *   {MK_FIELD_BYTES, stride, N}    N % 4 == 0, stride % 4 == 0, stride >= N;
+ *                                  the element hash is Keccak(le32(N) || bytes)
+ *   {MK_FIELD_STRUCT, stride, k}   plus its k flattened descendants (RAW,
+ *                                  BYTES, VARBYTES, STRUCT; no LIST) at
+ *                                  offsets inside the cell; stride % 4 == 0 and
+ *                                  covers every child; the element hash is the
+ *                                  struct hash.  The item struct counts as one
+ *                                  nesting level.
+ * Field hash = merkleHash of the count element hashes (hash.go:194-239):
+ * 128 / out_len items per chunk (out_len = len for RAW items, else 32), the
+ * last chunk short, no item = one chunk of 128 zero bytes, an odd level of
+ * more than one node padded with 128 zero bytes, and Keccak(top ||
+ * le64(count) || 0^24).  A list may stand at top level or inside a nested
+ * struct, several in one record; a list inside a list item is MK_EINVAL.
+ * Limits: at most 256 chunks per list field (cap <= 256 * 128 / out_len); the
+ * depth and entry limits above; and per record, along any one nesting path,
+ * the messages (each rounded up to 4), a list's 256-byte chunk pair, 32 bytes
+ * per level of its node stack (0 for a list of one chunk, else the bit length
+ * of ceil(chunks / 2): at most 8) and behind them a struct item's messages may
+ * sum to at most 640 bytes -- these layouts run 64 or 128 threads per
+ * workgroup.  Device entry points clamp count to cap and never read outside
+ * the slot; the host-buffer and handle entry points return MK_EINVAL,
+ * changing nothing, for a count above cap (or a stored length above its slot
+ * inside one of the first count items).
+ *
  * mk_ssz_struct_msg_len: the top-level struct's message length; for a layout
  * with MK_FIELD_STRUCT entries the scratch bytes per record instead, the
  * message lengths of the top-level struct and of every nested struct summed.
@@ -448,6 +480,7 @@ int mk_dev_ssz_merkle_hash_multi(mk_call* call, const void* const* d_shards, uin
 #define MK_FIELD_RAW 2
 #define MK_FIELD_VARBYTES 3
 #define MK_FIELD_STRUCT 4
+#define MK_FIELD_LIST 5
 typedef struct mk_field {
     uint32_t kind;
     uint32_t offset;

@@ -245,6 +245,7 @@ MK_FIELD_BYTES = 1
 MK_FIELD_RAW = 2
 MK_FIELD_VARBYTES = 3  # le32(L) || L bytes in a slot of 4 + len bytes
 MK_FIELD_STRUCT = 4    # a nested struct: len = the entries that follow and belong to it
+MK_FIELD_LIST = 5      # le32(count) || len cells; the next entry describes one item, its offset the stride
 
 
 class Field(ctypes.Structure):

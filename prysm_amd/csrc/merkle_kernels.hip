@@ -4142,3 +4142,5 @@ __global__ __launch_bounds__(256) void k_many_final(const uint8_t* __restrict__ 
 #include "kernels_tree.hip"
 // the deposit trie's roll back, fork point, audit and copy; after kernels_tree.hip: its audit helpers
 #include "kernels_trie_admin.hip"
+// records with list fields; k_struct_nested's column helpers
+#include "kernels_struct_list.hip"

@@ -36,6 +36,9 @@ __global__ void k_struct_fused(const uint8_t* rec, uint64_t n, StructSpec sp, ui
 // dynamic LDS NT * ns.peak bytes (NT = ns.threads)
 template <uint32_t NT>
 __global__ void k_struct_nested(const uint8_t* rec, uint64_t n, NestedSpec ns, uint4* roots);
+// the same with list fields (MK_FIELD_LIST): dynamic LDS NT * ls.peak bytes (NT = ls.threads: 128 or 64)
+template <uint32_t NT>
+__global__ void k_struct_list(const uint8_t* rec, uint64_t n, ListSpec ls, uint4* roots);
 template <int NB, int NRAW>
 __global__ void k_struct_reg(const uint8_t* rec, uint64_t n, StructSpec sp, uint32_t vec16, uint4* roots);
 // validator layout (kValOff/kValLen in merkle_kernels.hip), any n (a partial last group);

@@ -11,7 +11,7 @@ namespace {
 // ---- struct hashing ---------------------------------------------------------------
 // parsing and every check of the layout: struct_spec.cpp (no HIP, no device)
 int make_spec(const mk_field* fields, uint32_t nfields, uint32_t record_len, mk::HostSpec& sp) {
-    return mk::parse_struct_spec(fields, nfields, record_len, sp);
+    return mk::parse_struct_layout(fields, nfields, record_len, sp);
 }
 
 // k_struct_lock's compile-time layout: the SURVEY §8d ValidatorRecord
@@ -69,6 +69,18 @@ int launch_struct_roots(const void* d_rec, uint64_t n, const mk::HostSpec& sp, v
     if (sp.nested) {  // nested structs, variable-length byte fields: one launch, messages in LDS
         if ((uintptr_t)d_rec % 4) return fail(MK_EINVAL, "records of a nested layout must be 4-byte aligned");
         if (sp.rec_len == 0) return fail(MK_EINVAL, "record_len == 0");
+        if (sp.lists) {  // list fields: the longer program, down to one wave per workgroup
+            const mk::ListSpec& ls = sp.lprog;
+            const dim3 grid(ceil_div(n, ls.threads)), block(ls.threads);
+            const uint32_t lds = ls.threads * ls.peak;
+            if (ls.threads == mk::kListThreadsMax)
+                hipLaunchKernelGGL((mk::k_struct_list<128>), grid, block, lds, st, (const uint8_t*)d_rec, n, ls,
+                                   (uint4*)d_roots);
+            else
+                hipLaunchKernelGGL((mk::k_struct_list<64>), grid, block, lds, st, (const uint8_t*)d_rec, n, ls,
+                                   (uint4*)d_roots);
+            return launched();
+        }
         const mk::NestedSpec& ns = sp.prog;
         if (ns.threads == mk::kNestedThreadsMax)
             hipLaunchKernelGGL((mk::k_struct_nested<mk::kNestedThreadsMax>), dim3(ceil_div(n, ns.threads)),

@@ -119,6 +119,7 @@ int struct_tree_layout(const mk_field* fields, uint32_t nfields, uint32_t record
         const uint32_t slot = L.sp.kind[f] == MK_FIELD_VARBYTES ? 4 + L.sp.len[f] : L.sp.len[f];
         ext = std::max(ext, (L.sp.off[f] + slot + 3) & ~3u);
     }
+    if (L.sp.lists) ext = L.sp.ext;  // a list's slot, and item fields at offsets inside the cell: the parser's figure
     L.ext = ext;
     return MK_OK;
 }
@@ -179,7 +180,7 @@ int struct_tree_stage0(const StructTreeLayout& L, void* d_records, uint64_t n_ol
                            (const uint8_t*)d_records, d_idx, k_idx, n_old, n_app, L.sp.rec_len, L.ext, gath);
         HIPCHK(hipGetLastError());
         src = gath;
-        sp.rec_len = sp.prog.rec_len = L.ext;
+        sp.rec_len = sp.prog.rec_len = sp.lprog.rec_len = L.ext;
     }
     TRY(struct_launch_roots(src, T, sp, msg, roots, st));
     return list_tree_scatter(d_roots, d_idx, k_idx, n_old, n_app, 32, roots, st);

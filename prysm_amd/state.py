@@ -188,6 +188,134 @@ def pack_attestations(att: "Attestations", bitfield_cap: int = None):
     return rec, pending_attestation_fields(bitfield_cap)
 
 
+# ---- records with list fields (MK_FIELD_LIST): le32(count), then `cap` item cells ------------
+_LIST = _lib.MK_FIELD_LIST
+
+# types.pb.go field order; the values are dicts (or objects) keyed by the Go field names
+SLASHABLE_VOTE_SSZ = S.Struct("pb.SlashableVote", [
+    ("ValidatorIndices", S.Slice(_U64)), ("CustodyBitfield", _B), ("Data", S.Ptr(ATTESTATION_DATA_SSZ)),
+    ("AggregateSignature", _B)])
+ATTESTER_SLASHING_SSZ = S.Struct("pb.AttesterSlashing", [
+    ("SlashableVote_1", S.Ptr(SLASHABLE_VOTE_SSZ)), ("SlashableVote_2", S.Ptr(SLASHABLE_VOTE_SSZ))])
+DEPOSIT_SSZ = S.Struct("pb.Deposit", [
+    ("MerkleBranchHash32S", S.Slice(_B)), ("MerkleTreeIndex", _U64), ("DepositData", _B)])
+DEPOSIT_BRANCH_CAP = 32  # DepositContractTreeDepth nodes of 32 bytes
+
+
+def _shift(fields, base: int):
+    """The layout moved to record offset ``base`` (struct entries and item
+    descriptors keep their offset member: 0, or a stride)."""
+    out, skip = [], False
+    for kind, off, ln in fields:
+        out.append((kind, off if kind == _STRUCT or skip else off + base, ln))
+        skip = kind == _LIST  # the next entry is the item descriptor
+    return out
+
+
+def slashable_vote_record_len(indices_cap: int, bitfield_cap: int, signature_cap: int = 96) -> int:
+    return 4 + 8 * indices_cap + 4 + bitfield_cap + 192 + 4 + signature_cap
+
+
+def slashable_vote_fields(indices_cap: int, bitfield_cap: int, signature_cap: int = 96):
+    """The SlashableVote layout: the validator indices as a list slot of
+    ``indices_cap`` uint64 cells, the custody bitfield slot, AttestationData
+    (192 B), the aggregate signature slot; 14 entries."""
+    if bitfield_cap % 4 or signature_cap % 4:
+        raise ValueError("bitfield and signature capacities must be multiples of 4")
+    o1 = 4 + 8 * indices_cap
+    o2 = o1 + 4 + bitfield_cap
+    return ([(_LIST, 0, indices_cap), (_RAW, 8, 8), (_VAR, o1, bitfield_cap), (_STRUCT, 0, len(_ATT_DATA_FIELDS))] +
+            _shift(_ATT_DATA_FIELDS, o2) + [(_VAR, o2 + 192, signature_cap)])
+
+
+def _put_var(rec: np.ndarray, off: int, cap: int, b: bytes, what: str) -> None:
+    if len(b) > cap:
+        raise ValueError(f"{what} of {len(b)} bytes in a {cap}-byte slot")
+    rec[off:off + 4] = np.frombuffer(_st.pack("<I", len(b)), dtype=np.uint8)
+    rec[off + 4:off + 4 + len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
+
+
+def _put_vote(rec: np.ndarray, v, indices_cap: int, bitfield_cap: int, signature_cap: int) -> None:
+    idx = np.asarray(S._field(v, "ValidatorIndices"), dtype="<u8").reshape(-1)
+    if idx.size > indices_cap:
+        raise ValueError(f"{idx.size} validator indices in a slot of {indices_cap}")
+    rec[0:4] = np.frombuffer(_st.pack("<I", idx.size), dtype=np.uint8)
+    rec[4:4 + 8 * idx.size] = idx.view(np.uint8)
+    o1 = 4 + 8 * indices_cap
+    o2 = o1 + 4 + bitfield_cap
+    _put_var(rec, o1, bitfield_cap, S._field(v, "CustodyBitfield"), "custody bitfield")
+    d = S._field(v, "Data")
+    data = rec[o2:o2 + 192]
+    for name, off in (("Slot", 0), ("Shard", 8), ("JustifiedEpoch", 144), ("JustifiedSlot", 184)):
+        data[off:off + 8] = np.frombuffer(_st.pack("<Q", int(S._field(d, name))), dtype=np.uint8)
+    for name, off in (("BeaconBlockRootHash32", 16), ("EpochBoundaryRootHash32", 48), ("ShardBlockRootHash32", 80),
+                      ("LatestCrosslinkRootHash32", 112), ("JustifiedBlockRootHash32", 152)):
+        b = bytes(S._field(d, name))
+        if len(b) != 32:
+            raise ValueError(f"{name} of {len(b)} bytes in a 32-byte field")
+        data[off:off + 32] = np.frombuffer(b, dtype=np.uint8)
+    _put_var(rec, o2 + 192, signature_cap, S._field(v, "AggregateSignature"), "aggregate signature")
+
+
+def pack_slashable_votes(votes, indices_cap: int, bitfield_cap: int, signature_cap: int = 96):
+    """[]*SlashableVote as flat records: (records (n, record_len) uint8, fields)."""
+    fields = slashable_vote_fields(indices_cap, bitfield_cap, signature_cap)
+    rec = np.zeros((len(votes), slashable_vote_record_len(indices_cap, bitfield_cap, signature_cap)), dtype=np.uint8)
+    for i, v in enumerate(votes):
+        _put_vote(rec[i], v, indices_cap, bitfield_cap, signature_cap)
+    return rec, fields
+
+
+def attester_slashing_fields(indices_cap: int, bitfield_cap: int, signature_cap: int = 96):
+    """AttesterSlashing: its two SlashableVotes by value, one behind the
+    other (a list inside a nested struct); 30 entries."""
+    vote = slashable_vote_fields(indices_cap, bitfield_cap, signature_cap)
+    vlen = slashable_vote_record_len(indices_cap, bitfield_cap, signature_cap)
+    return [(_STRUCT, 0, len(vote))] + vote + [(_STRUCT, 0, len(vote))] + _shift(vote, vlen)
+
+
+def pack_attester_slashings(slashings, indices_cap: int, bitfield_cap: int, signature_cap: int = 96):
+    """[]*AttesterSlashing as flat records: (records, fields)."""
+    vlen = slashable_vote_record_len(indices_cap, bitfield_cap, signature_cap)
+    rec = np.zeros((len(slashings), 2 * vlen), dtype=np.uint8)
+    for i, s in enumerate(slashings):
+        _put_vote(rec[i, :vlen], S._field(s, "SlashableVote_1"), indices_cap, bitfield_cap, signature_cap)
+        _put_vote(rec[i, vlen:], S._field(s, "SlashableVote_2"), indices_cap, bitfield_cap, signature_cap)
+    return rec, attester_slashing_fields(indices_cap, bitfield_cap, signature_cap)
+
+
+_DEP_INDEX = 8 + 32 * DEPOSIT_BRANCH_CAP  # the branch slot (4 + 1024 B) rounded up to 8
+
+
+def deposit_record_len(data_cap: int) -> int:
+    return _DEP_INDEX + 8 + 4 + data_cap
+
+
+def deposit_fields(data_cap: int):
+    """Deposit: the Merkle branch as a list slot of 32 cells of 32 bytes,
+    the tree index, the deposit data slot; 4 entries."""
+    if data_cap % 4:
+        raise ValueError("deposit data capacity must be a multiple of 4")
+    return [(_LIST, 0, DEPOSIT_BRANCH_CAP), (_BY, 32, 32), (_RAW, _DEP_INDEX, 8), (_VAR, _DEP_INDEX + 8, data_cap)]
+
+
+def pack_deposits(deposits, data_cap: int):
+    """[]*Deposit as flat records: (records, fields)."""
+    rec = np.zeros((len(deposits), deposit_record_len(data_cap)), dtype=np.uint8)
+    for i, d in enumerate(deposits):
+        branch = [bytes(b) for b in S._field(d, "MerkleBranchHash32S")]
+        if len(branch) > DEPOSIT_BRANCH_CAP:
+            raise ValueError(f"Merkle branch of {len(branch)} nodes in a slot of {DEPOSIT_BRANCH_CAP}")
+        if any(len(b) != 32 for b in branch):
+            raise ValueError("Merkle branch nodes must be 32 bytes")
+        rec[i, 0:4] = np.frombuffer(_st.pack("<I", len(branch)), dtype=np.uint8)
+        rec[i, 4:4 + 32 * len(branch)] = np.frombuffer(b"".join(branch), dtype=np.uint8)
+        rec[i, _DEP_INDEX:_DEP_INDEX + 8] = np.frombuffer(_st.pack("<Q", int(S._field(d, "MerkleTreeIndex"))),
+                                                          dtype=np.uint8)
+        _put_var(rec[i], _DEP_INDEX + 8, data_cap, S._field(d, "DepositData"), "deposit data")
+    return rec, deposit_fields(data_cap)
+
+
 def pack_eth1_votes(votes: np.ndarray, counts: np.ndarray) -> np.ndarray:
     """[]*Eth1DataVote as (v, 72) uint8 records of ETH1_VOTE_FIELDS."""
     v = len(votes)
