@@ -159,8 +159,11 @@ def flatten(typ, caps):
     entries, size, put = _lay(typ, list(caps), 0, False)
     rec_len = _align4(size)
 
-    def pack(v):
-        buf = bytearray(rec_len)
+    def pack(v, fill=None):
+        """``fill``: rec_len bytes the record starts from (the padding, the slots'
+        unused tails and the cells beyond a count keep them); None: zeros."""
+        buf = bytearray(rec_len) if fill is None else bytearray(fill)
+        assert len(buf) == rec_len
         put(buf, 0, v)
         return bytes(buf)
     return entries[1:], rec_len, pack  # without the top-level struct's own entry

@@ -4,8 +4,9 @@ merkleHash at random sizes, item lengths and byte offsets (a case is capped
 at 3 MiB and 2^17.5 items, at most 16,384 windows: the spread leaf pass, the
 list tree and the lane-pair k_wave3 passes; the throughput leaf passes start
 above 2^17 windows and belong to tests/test_gpu_ws_contract.py),
-many lists per call, struct roots of random layouts (both struct kernels
-and the generic one), deposit tries grown by random batches with the
+many lists per call, struct roots of random flat layouts (kinds 1 and 2: both
+flat struct kernels and the generic one; nested, []byte and list-field layouts
+are fuzzed in tests/test_gpu_struct_fuzz.py), deposit tries grown by random batches with the
 per-log check, and MerkleRoot.  Sizes keep the oracle to seconds.
 _item_len and _layout are shared with the resident-tree fuzz
 (tests/tree_fuzz_plan.py, test_gpu_tree_fuzz.py)."""
