@@ -945,6 +945,103 @@ int mk_tree_set_copy(mk_call* call, mk_tree_set* dst, mk_tree_set* src);
 int mk_tree_set_reserve(mk_call* call, mk_tree_set* s, uint32_t tree, uint64_t capacity);
 uint64_t mk_tree_set_capacity(const mk_tree_set* s, uint32_t tree);
 
+/* ---- resident trees: an update taken back through an undo journal --- */
+/* An update overwrites the changed values, their level-0 entries and their
+ * ancestors: about changed x depth nodes.  mk_dev_ssz_trees_journal saves
+ * exactly those before the update runs, mk_dev_ssz_trees_restore writes them
+ * back: an update is undone without a hash and without a second copy of the
+ * state.
+ * journal takes the very array mk_dev_ssz_trees_update is about to get (the
+ * same kinds, d_idx / k_idx, n_old / n_new) and is enqueued BEFORE that update
+ * on the same stream -- and, for a tree with d_values == NULL, before the
+ * caller writes the new bytes.  ONE launch (k_trees_journal) saves into
+ * d_journal, per tree: the work items -- the k_idx listed indices and, when
+ * n_new > n_old > 0, one more for the last old value, on whose ancestors every
+ * stored ancestor of an appended chunk lies -- each as 8 bytes of index, the
+ * old value, its 32-B level-0 entry (STRUCT / BYTES) and node (chunk >> d) of
+ * every level d = 1 .. D of the old tree (the layout rule: the resident list
+ * tree above); then the tree's 32-B root.  Per call: the container message and
+ * the container root.  A slot per (work item, level) at a fixed position: two
+ * work items under one node both save it, nothing is compacted, the launch has
+ * no atomics and waits for nothing.  A listed index >= n_old stands for the
+ * last old value (the update ignores it; either way the journal is right); a
+ * tree with n_old == 0 saves its root only.  No byte of a value buffer or a
+ * level 0 at or beyond n_old values is part of the old state -- the three
+ * kinds' kernels read a level-1 window, a raw chunk and every record or
+ * element only below the count they are given -- so none is saved, and what an
+ * update appended stays behind the restored end, unspecified as after a shrink.
+ * restore takes the same array; the index LISTS (d_idx) and d_values are not
+ * read -- they may be NULL or reused -- because the indices come from the
+ * journal; kind, item_len, the buffers, capacity, k_idx, n_old and n_new must
+ * be what journal got, and n_old is the count to return to.  ONE launch
+ * (k_trees_restore) scatters every saved piece back; duplicates carry equal
+ * bytes.  Afterwards every byte the layout contract specifies for n_old values
+ * is what it was when journal ran: values [0, n_old), level 0, the nodes
+ * within the old counts on levels up to the old top, the root, the message and
+ * the container root.  Nodes and levels beyond that stay unspecified.  Several
+ * records are undone newest first, in stream order.
+ * d_journal is 16-B aligned, mk_ssz_trees_journal_bytes long (0 for an array
+ * the calls would refuse) and nothing beyond that is written; it depends on
+ * the counts, k_idx, item_len and container_len only.  Every argument is
+ * checked before a device is looked up, by the rules of
+ * mk_dev_ssz_trees_update; a null or misaligned journal is MK_EINVAL, a short
+ * one MK_ENOMEM.  Both upload nothing, allocate nothing, never synchronise and
+ * can be captured into a hipGraph. */
+uint64_t mk_ssz_trees_journal_bytes(const mk_tree_update* trees, uint32_t ntrees, uint32_t container_len);
+int mk_dev_ssz_trees_journal(mk_call* call, const mk_tree_update* trees, uint32_t ntrees, const void* d_container,
+                             uint32_t container_len, const void* d_container_root32, void* d_journal,
+                             uint64_t journal_bytes, void* stream);
+int mk_dev_ssz_trees_restore(mk_call* call, const mk_tree_update* trees, uint32_t ntrees, void* d_container,
+                             uint32_t container_len, void* d_container_root32, const void* d_journal,
+                             uint64_t journal_bytes, void* stream);
+/* Checkpoints of a set: apply a block, verify the state root,
+ * keep it or roll it back; keep the last slots undoable for about their change
+ * volume instead of a clone each.
+ * checkpoint: flushes what is pending (journaled only if a checkpoint is open
+ *   already), opens a checkpoint and returns its id; ids only grow.  With
+ *   MK_CHECKPOINTS_MAX open it is MK_EINVAL and nothing changes.
+ * While a checkpoint is open every flush is one record: the flush enqueues
+ *   mk_dev_ssz_trees_journal between its upload and its update, into a journal
+ *   the set owns (it grows by doubling; journal_reserve gives it room ahead of
+ *   a slot), and keeps the per-tree n_old, n_new, k_idx and the offset on the
+ *   host.  A change that does not climb -- assign, a flush that rebuilds a tree
+ *   at its kind's dirty share or grows it past its capacity, truncate, erase --
+ *   writes a full record of that tree instead: its live part copied by the copy
+ *   launch (mk_dev_ssz_trees_copy) into memory the journal owns, before the
+ *   change.  A record counts only after the synchronise the flush already does:
+ *   a failed flush can still be tried again.  add is MK_EINVAL while a
+ *   checkpoint is open.
+ * rollback(id): drops the pending changes, undoes every record made since
+ *   checkpoint id newest first (journals restored, full records copied home),
+ *   restores the counts and the message, closes id and every later checkpoint,
+ *   and ends with one flush with nothing dirty that brings the trees' roots in
+ *   the message and the message's root up to date (the journals of a set hold
+ *   no container), under the call's synchronise; a full record's copy home
+ *   synchronises too.  Capacity is not part of the state: a tree that grew
+ *   stays grown.  An unknown or closed id is MK_EINVAL and nothing changes.
+ * release(id): forgets checkpoint id and every earlier one and frees the
+ *   records written before the first checkpoint that remains; with none
+ *   remaining the journal is empty and flushes stop journaling.
+ *   A device error (MK_EHIP) in the middle of a roll back leaves some records
+ *   undone and the checkpoint open: the set's content is then undefined, and
+ *   the caller frees it or assigns every tree.
+ * journal_bytes: the bytes of HBM the open checkpoints hold (journals and full
+ *   records).  journal_capacity: the bytes allocated for the journals; the
+ *   front a release frees is taken back before the buffer is made larger, so
+ *   a ring of checkpoints whose oldest is released every slot keeps it at
+ *   about twice its live records.  journal_reserve(bytes): room for that many
+ *   bytes of live journal.  clone / copy copy the state, not the journal; a copy INTO a set
+ *   with open checkpoints is MK_EINVAL.  The calls run under the set's mutex.
+ * mk_list_tree and its siblings have no checkpoints: they have no pending log;
+ *   a set of one tree covers them. */
+#define MK_CHECKPOINTS_MAX 64
+int mk_tree_set_checkpoint(mk_call* call, mk_tree_set* s, uint64_t* id);
+int mk_tree_set_rollback(mk_call* call, mk_tree_set* s, uint64_t id);
+int mk_tree_set_release(mk_call* call, mk_tree_set* s, uint64_t id);
+uint64_t mk_tree_set_journal_bytes(const mk_tree_set* s);
+uint64_t mk_tree_set_journal_capacity(const mk_tree_set* s);
+int mk_tree_set_journal_reserve(mk_call* call, mk_tree_set* s, uint64_t bytes);
+
 /* ---- resident trees audited on the device ------------------------- */
 /* Is a resident tree what its values say it is?  Every stored node is checked
  * against what is stored below it, read-only and in HBM.  len0 = item_len for

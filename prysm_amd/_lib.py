@@ -224,6 +224,15 @@ _SIGS = {
     "mk_tree_set_copy": (_int, [_cp, _vp, _vp]),
     "mk_tree_set_reserve": (_int, [_cp, _vp, _u32, _u64]),
     "mk_tree_set_capacity": (_u64, [_vp, _u32]),
+    "mk_ssz_trees_journal_bytes": (_u64, [_vp, _u32, _u32]),
+    "mk_dev_ssz_trees_journal": (_int, [_cp, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "mk_dev_ssz_trees_restore": (_int, [_cp, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "mk_tree_set_checkpoint": (_int, [_cp, _vp, _vp]),
+    "mk_tree_set_rollback": (_int, [_cp, _vp, _u64]),
+    "mk_tree_set_release": (_int, [_cp, _vp, _u64]),
+    "mk_tree_set_journal_bytes": (_u64, [_vp]),
+    "mk_tree_set_journal_capacity": (_u64, [_vp]),
+    "mk_tree_set_journal_reserve": (_int, [_cp, _vp, _u64]),
     "mk_ssz_trees_audit_workspace_bytes": (_u64, [_vp, _u32]),
     "mk_dev_ssz_trees_audit": (_int, [_cp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u64, _vp]),
     "mk_list_tree_audit": (_int, [_cp, _vp, _vp]),
@@ -259,6 +268,7 @@ MK_TREE_BYTES = 3   # mk_dev_ssz_bytes_list_tree_update's tree
 MK_TREES_MAX = 16
 MK_NO_CONTAINER = 0xFFFFFFFF
 MK_CONTAINER_MAX = 4096
+MK_CHECKPOINTS_MAX = 64
 # the dirty share from which a resident tree's host handle rebuilds instead of climbing: count / DIV
 # (MK_*_TREE_REBUILD_DIV in csrc/list_tree_api.cpp, struct_tree_api.cpp, bytes_tree_api.cpp)
 LIST_TREE_REBUILD_DIV = 512
@@ -338,6 +348,10 @@ def load():
                                      "(no CPU fallback exists)")
     L = ctypes.CDLL(path)
     for name, (res, args) in _SIGS.items():
+        # an older build named by PRYSM_MERKLE_LIB (a parent commit's, for A/B timing) may lack the newest entries;
+        # the shipped library may not (__graft_entry__.build() checks every header symbol)
+        if path != LIB_PATH and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,7 @@
 #include "tree_compact.hpp"
 #include "tree_copy.hpp"
 #include "tree_diff.hpp"
+#include "tree_journal.hpp"
 
 namespace mk {
 
@@ -1135,5 +1136,83 @@ __global__ __launch_bounds__(64) void k_diff_reports(DiffReport* reports, uint32
     reports[threadIdx.x].total = 0;
     reports[threadIdx.x].first_index = ~0ull;
 }
+
+// ----------------------------------------------------------------------------
+// Undo journal of resident trees (the slot map:
+// tree_journal.hpp).  k_trees_journal runs BEFORE an update of the same trees
+// on the same stream and saves what that update may overwrite of the old
+// state: per work item (a listed index, or the last old value when the list
+// grows) the value, its level-0 entry and node (chunk >> d) of every stored
+// level, then the tree's root, and the container message with its root.
+// k_trees_restore is the same walk with the two sides swapped; a work item's
+// value index then comes from the journal (clamped again, so a journal that
+// was never written still reaches no byte outside the tree).  Slice blockIdx.y
+// of the grid is one tree, the slice behind the trees the container; a thread
+// moves one piece of tree_journal.hpp and writes nothing else: a gather and a
+// scatter, no counters, no hand-off.  Two work items under one node write the
+// same bytes to it on the way back.
+namespace {
+
+__device__ __forceinline__ void journal_move(uint8_t* dst, const uint8_t* src, uint32_t len) {
+    if (len == 16)
+        *reinterpret_cast<copy_global_u32x4*>((uintptr_t)dst) = *reinterpret_cast<const copy_global_u32x4*>((uintptr_t)src);
+    else if (len == 8)
+        *reinterpret_cast<uint64_t*>(dst) = *reinterpret_cast<const uint64_t*>(src);
+    else if (len == 4)
+        *reinterpret_cast<uint32_t*>(dst) = *reinterpret_cast<const uint32_t*>(src);
+    else
+        *dst = *src;
+}
+
+template <bool RESTORE>
+__device__ __forceinline__ void journal_run(const JournalArgs& g) {
+    const uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x, gid = g0 + threadIdx.x;
+    if (blockIdx.y >= g.ntrees) {  // the container: 4-byte pieces of the message (the last one in bytes), then of its root
+        const uint32_t words = (g.container_len + 3) / 4;
+        if (gid >= words + 8) return;
+        uint8_t *t, *j;
+        uint32_t len = 4;
+        if (gid < words) {
+            t = g.container + 4 * gid;
+            j = g.jr_container + 4 * gid;
+            if (4 * gid + 4 > g.container_len) len = g.container_len - 4 * (uint32_t)gid;  // 1 .. 3
+        } else {
+            t = g.container_root + 4 * (gid - words);
+            j = g.jr_container + journal_up16(g.container_len) + 4 * (gid - words);
+        }
+        if (len == 4) {
+            journal_move(RESTORE ? t : j, RESTORE ? j : t, 4);
+        } else {
+            for (uint32_t b = 0; b < len; ++b) (RESTORE ? t : j)[b] = (RESTORE ? j : t)[b];
+        }
+        return;
+    }
+    const JournalSeg& s = g.s[blockIdx.y];
+    const JournalShape sh = journal_shape(s.n_old, s.n_new, s.capacity, s.k_idx, s.item_len, s.level0 != nullptr);
+    if (g0 >= journal_pieces(sh, s.unit)) return;  // the whole block: another segment is the larger one
+    const JournalPiece pc = journal_piece(sh, s.unit, gid);
+    if (pc.kind == kJournalNone) return;
+    uint8_t* j = s.jr + pc.jr_off;
+    if (pc.kind == kJournalRoot) {
+        uint8_t* t = s.root + pc.at;
+        journal_move(RESTORE ? t : j, RESTORE ? j : t, 4);
+        return;
+    }
+    const uint64_t* listed = RESTORE ? reinterpret_cast<const uint64_t*>(s.jr) : s.idx;
+    const uint64_t x = journal_value(sh, pc.w, pc.w < sh.k_idx ? listed[pc.w] : 0);
+    if (pc.kind == kJournalIndex) {
+        if (!RESTORE) *reinterpret_cast<uint64_t*>(j) = x;
+        return;
+    }
+    uint8_t* t = pc.kind == kJournalItem     ? s.items + x * s.item_len + pc.at
+                 : pc.kind == kJournalLevel0 ? s.level0 + 32 * x + pc.at
+                                             : s.levels + journal_node_off(sh, x, pc.level) + pc.at;
+    journal_move(RESTORE ? t : j, RESTORE ? j : t, pc.len);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_trees_journal(JournalArgs g) { journal_run<false>(g); }
+__global__ __launch_bounds__(256) void k_trees_restore(JournalArgs g) { journal_run<true>(g); }
 
 }  // namespace mk

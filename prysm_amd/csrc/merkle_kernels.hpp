@@ -350,6 +350,29 @@ __global__ void k_trees_diff(TreesDiffArgs g);
 // count reports cleared to (0, ~0)
 __global__ void k_diff_reports(DiffReport* reports, uint32_t count);
 
+// Undo journal of up to kTreesMax resident trees and their container (tree_journal_api.cpp; the
+// slot map: tree_journal.hpp).  The descriptors by value, 1.5 KB of kernel arguments: nothing is uploaded.
+struct JournalSeg {
+    uint8_t *items, *level0, *levels, *root;  // the tree; level0 NULL for a list tree
+    const uint64_t* idx;                      // journal: the update's k_idx indices (device); restore: unused
+    uint8_t* jr;                              // the tree's region of the journal, 16-B aligned
+    uint64_t n_old, n_new, capacity, k_idx;
+    uint32_t item_len;
+    uint32_t unit;  // 16, 8 or 1: bytes per value piece; divides item_len and the value buffer's address
+};
+struct JournalArgs {
+    JournalSeg s[kTreesMax];  // segment blockIdx.y < ntrees; segment ntrees: the container
+    uint8_t* container;       // the hash message, 4-B aligned; NULL: no container
+    uint8_t* container_root;  // 32 bytes, 4-B aligned
+    uint8_t* jr_container;    // up16(container_len) bytes of message, then the 32 bytes of its root
+    uint32_t container_len;
+    uint32_t ntrees;
+};
+// grid (blocks of the largest segment, segments), 256 threads, one piece per thread; a block beyond its
+// segment's pieces returns at once.  k_trees_journal: tree -> journal; k_trees_restore: journal -> tree
+__global__ void k_trees_journal(JournalArgs g);
+__global__ void k_trees_restore(JournalArgs g);
+
 // The resident deposit trie rolled back, compared, audited and copied (kernels_trie_admin.hip,
 // trie_admin_api.cpp; the rules: trie_admin.hpp).
 // one wave: the straddling nodes of a roll back to c <= count stored along the as-of chain, the root to root_out

@@ -357,6 +357,17 @@ int tree_diff(TreeHandle* a, TreeHandle* b, uint64_t* idx_out, uint64_t max_out,
 int trees_update_workspace(const mk_tree_update* trees, uint32_t ntrees, uint64_t* bytes);
 int trees_update(const mk_tree_update* trees, uint32_t ntrees, void* d_container, uint32_t container_len,
                  void* d_container_root32, void* d_ws, uint64_t ws_bytes, hipStream_t st);
+// every argument rule of mk_dev_ssz_trees_update but the workspace's size, for the calls that take the same
+// array (tree_journal_api.cpp); d_ws16: any 16-B aligned pointer of the caller's; lists == false: the index
+// arrays and the staged values are not looked at.  No device needed.
+int trees_update_check(const mk_tree_update* trees, uint32_t ntrees, const void* d_container, uint32_t container_len,
+                       const void* d_container_root32, const void* d_ws16, bool lists);
+// ---- the undo journal of resident trees (tree_journal_api.cpp) ---------------------
+// mk_ssz_trees_journal_bytes with its error; mk_dev_ssz_trees_journal / _restore after bind_stream(): every
+// check, then the one launch on st
+int trees_journal_bytes(const mk_tree_update* trees, uint32_t ntrees, uint32_t container_len, uint64_t* bytes);
+int trees_journal(bool restore, const mk_tree_update* trees, uint32_t ntrees, void* d_container, uint32_t container_len,
+                  void* d_container_root32, void* d_journal, uint64_t journal_bytes, hipStream_t st);
 int struct_tree_stage0_roots(const StructTreeLayout& L, const void* d_records, uint64_t n_new, uint64_t T,
                              const void* d_values, void* d_roots, void* d_scratch, const void** d_new_roots,
                              hipStream_t st);

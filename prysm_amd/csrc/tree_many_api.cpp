@@ -108,8 +108,9 @@ int check_container(const mk_tree_update* trees, uint32_t ntrees, uint32_t conta
 }
 
 // every pointer: each kind's own checks, and d_level0 against the kind
+// (lists: the index arrays and the staged values too -- a restore reads neither)
 int check_ptrs(const mk_tree_update* trees, uint32_t ntrees, const void* d_container, uint32_t container_len,
-               const void* d_container_root32, const void* d_ws) {
+               const void* d_container_root32, const void* d_ws, bool lists = true) {
     if (!d_ws || ((uintptr_t)d_ws % 16)) return fail(MK_EINVAL, "null or misaligned (16 B) workspace");
     for (uint32_t i = 0; i < ntrees; ++i) {
         const mk_tree_update& t = trees[i];
@@ -119,12 +120,12 @@ int check_ptrs(const mk_tree_update* trees, uint32_t ntrees, const void* d_conta
         } else if (t.kind == MK_TREE_STRUCT) {
             if (!t.d_level0) return fail(MK_EINVAL, "tree %u: null d_level0 (the struct roots)", i);
             TRY(struct_tree_check_ptrs(t.d_items, t.n_new, t.capacity, t.d_level0, t.d_levels, t.d_root32, d_ws));
-            if ((uintptr_t)t.d_values % 4) return fail(MK_EINVAL, "tree %u: new records not 4-byte aligned", i);
+            if (lists && (uintptr_t)t.d_values % 4) return fail(MK_EINVAL, "tree %u: new records not 4-byte aligned", i);
         } else {
             if (!t.d_level0) return fail(MK_EINVAL, "tree %u: null d_level0 (the element digests)", i);
             TRY(bytes_tree_check_ptrs(t.d_items, t.n_new, t.capacity, t.d_level0, t.d_levels, t.d_root32, d_ws));
         }
-        if (t.k_idx && (!t.d_idx || ((uintptr_t)t.d_idx % 8)))
+        if (lists && t.k_idx && (!t.d_idx || ((uintptr_t)t.d_idx % 8)))
             return fail(MK_EINVAL, "tree %u: null or misaligned index array", i);
     }
     if (container_len && (!d_container || !d_container_root32 || ((uintptr_t)d_container % 4) ||
@@ -266,6 +267,15 @@ int trees_update_workspace(const mk_tree_update* trees, uint32_t ntrees, uint64_
     TRY(make_plan(trees, ntrees, P));
     *bytes = P.total;
     return MK_OK;
+}
+
+int trees_update_check(const mk_tree_update* trees, uint32_t ntrees, const void* d_container, uint32_t container_len,
+                       const void* d_container_root32, const void* d_ws16, bool lists) {
+    WsLayout P;
+    uint32_t nparts = 0;
+    TRY(make_plan(trees, ntrees, P));
+    TRY(check_container(trees, ntrees, container_len, &nparts));
+    return check_ptrs(trees, ntrees, d_container, container_len, d_container_root32, d_ws16, lists);
 }
 
 int trees_update(const mk_tree_update* trees, uint32_t ntrees, void* d_container, uint32_t container_len,

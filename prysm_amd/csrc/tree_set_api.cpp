@@ -30,6 +30,31 @@ struct mk_tree_set {
     void* host = nullptr;           // pinned staging: the message, then every tree's indices and values
     size_t host_cap = 0;
     DevBuf stage, ws, croot;  // the staging buffer in HBM (the message at its front), workspace, container root
+    // ---- checkpoints ----
+    // One record per flush made while a checkpoint is open (and per assign / truncate / erase): the journal of
+    // the flush's update (mk_dev_ssz_trees_journal over the flush's own array, no container: a roll back ends
+    // with a flush that brings the message and its root up to date), and a full copy of every tree that did
+    // not climb -- a handle of its own, taken before the change by the copy launch.
+    struct Record {
+        bool climbed = false;            // a journal at [off, off + bytes) of `journal`
+        uint64_t off = 0, bytes = 0;
+        uint32_t nt = 0;
+        uint64_t n_old[MK_TREES_MAX] = {}, n_new[MK_TREES_MAX] = {}, k_idx[MK_TREES_MAX] = {};
+        std::vector<std::pair<uint32_t, TreeHandle*>> full;  // (tree, what it was)
+    };
+    struct Checkpoint {
+        uint64_t id = 0;
+        size_t first_record = 0;       // the records made since
+        uint64_t used = 0;             // the journal's fill when it was opened
+        std::vector<uint64_t> counts;  // every tree's
+        std::vector<uint8_t> msg;      // the host message
+    };
+    std::vector<Checkpoint> cps;  // the open ones, ids ascending
+    std::vector<Record> records;
+    Record next;           // of the flush in flight: counts only after its synchronise (flushed)
+    uint64_t next_id = 1;
+    DevBuf journal;
+    uint64_t used = 0, base = 0;  // records live in [base, used)
 };
 
 namespace {
@@ -53,11 +78,108 @@ int bind_set(mk_tree_set* s) {
     return MK_OK;
 }
 
+// the part of a tree's mk_tree_update that is the tree itself
+void tree_desc(const mk_tree_set::Tree& t, mk_tree_update& u) {
+    u.kind = t.kind;
+    u.item_len = t.h->item_len;
+    u.d_items = t.h->items.p;
+    u.d_level0 = t.h->level0.p;
+    u.d_levels = t.h->levels.p;
+    u.capacity = t.h->cap;
+    u.fields = t.fields.empty() ? nullptr : t.fields.data();
+    u.nfields = (uint32_t)t.fields.size();
+    u.container_off = t.coff;
+    u.d_root32 = t.h->root.p;
+}
+
+void drop_record(mk_tree_set::Record& r) {
+    for (auto& f : r.full) tree_free(f.second);
+    r = mk_tree_set::Record();
+}
+
+// tree i as it is now, kept in record r (once: a flush that is tried again keeps the first copy)
+int full_record(mk_tree_set* s, uint32_t i, mk_tree_set::Record& r) {
+    for (const auto& f : r.full)
+        if (f.first == i) return MK_OK;
+    TreeHandle* c = nullptr;
+    TRY(tree_clone(s->trees[i].h, &c));
+    r.full.emplace_back(i, c);
+    return MK_OK;
+}
+
+// An immediate change of tree i (assign, truncate, erase) under an open
+// checkpoint: its full record is a record of its own, filed when the change
+// succeeded -- the record of a flush in flight (s->next) is not touched.  A
+// flush that failed before may have left the tree half written and kept the
+// copy it took first: that copy is what the tree was, so it moves here.
+int immediate_begin(mk_tree_set* s, uint32_t i, mk_tree_set::Record& r) {
+    if (s->cps.empty()) return MK_OK;
+    for (size_t f = 0; f < s->next.full.size(); ++f)
+        if (s->next.full[f].first == i) {
+            r.full.push_back(s->next.full[f]);
+            s->next.full.erase(s->next.full.begin() + f);
+            return MK_OK;
+        }
+    TRY(bind_set(s));
+    return full_record(s, i, r);
+}
+void immediate_end(mk_tree_set* s, mk_tree_set::Record& r, int rc) {
+    if (r.full.empty()) return;
+    if (rc)
+        drop_record(r);
+    else
+        s->records.push_back(std::move(r));
+}
+
+// the record in flight counts
+void commit_record(mk_tree_set* s) {
+    if (!s->next.climbed && s->next.full.empty()) return;
+    if (s->next.climbed) s->used = s->next.off + s->next.bytes;
+    s->records.push_back(std::move(s->next));
+    s->next = mk_tree_set::Record();
+}
+
+// Room for `need` more bytes behind `used`.  The front that release() freed,
+// [0, base), is taken back first: the live part [base, used) moves to offset 0
+// (through a new buffer, so the two ranges never overlap) and every record's
+// offset and every checkpoint's fill move with it.  The buffer is only made
+// larger -- by doubling -- when the live part plus `need` does not fit, so a
+// ring of checkpoints whose oldest is released every slot holds a journal of
+// about twice its live records, however many slots went through it.
+int journal_room(mk_tree_set* s, uint64_t need) {
+    if (s->journal.cap >= s->used + need) return MK_OK;
+    const uint64_t live = s->used - s->base;
+    size_t cap = std::max<size_t>(s->journal.cap, (size_t)64 << 10);
+    while (cap < live + need) cap *= 2;
+    void* p = nullptr;
+    if (hipMalloc(&p, cap) != hipSuccess) return fail(MK_ENOMEM, "hipMalloc(%zu) failed", cap);
+    hipStream_t st = ctx()->stream;
+    if ((live && hipMemcpyAsync(p, (uint8_t*)s->journal.p + s->base, live, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) {  // also: nothing enqueued still reads the old buffer
+        (void)hipFree(p);
+        return fail(MK_EHIP, "moving the journal failed");
+    }
+    if (s->journal.p) (void)hipFree(s->journal.p);
+    s->journal.p = p;
+    s->journal.cap = cap;
+    for (auto& r : s->records)
+        if (r.climbed) r.off -= s->base;
+    for (auto& c : s->cps) c.used -= s->base;
+    s->used = live;
+    s->base = 0;
+    return MK_OK;
+}
+
 // Everything pending onto the device and every root brought up to date,
 // enqueued on the context's stream; the caller adds its read-back,
 // synchronises and calls flushed().  Nothing to do when nothing changed.
-int flush(mk_tree_set* s) {
+// While a checkpoint is open (and journaling is not switched off: the flush
+// that ends a roll back) the flush writes a record: a full copy of every tree
+// that does not climb before it is built, and the journal launch between the
+// upload and the update.
+int flush(mk_tree_set* s, bool journaling = true) {
     if (!s->dirty || s->trees.empty()) return MK_OK;
+    const bool jr = journaling && !s->cps.empty();
     const uint32_t nt = (uint32_t)s->trees.size();
     hipStream_t st = ctx()->stream;
     for (uint32_t i = 0; i < nt; ++i) s->pend[i].cap = s->trees[i].h->cap;
@@ -90,6 +212,7 @@ int flush(mk_tree_set* s) {
         u.n_old = p.n_old;
         u.n_new = p.n_new;
         if (p.action != sp::kClimb) {  // built here: enters the update with nothing dirty
+            if (jr) TRY(full_record(s, i, s->next));
             TRY(tree_write_through_build(t.h, p.n_old, p.n_new, p.new_cap, d_idx, p.k_idx, d_vals, st));
             u.n_old = p.n_new;
         } else if (T) {
@@ -97,16 +220,21 @@ int flush(mk_tree_set* s) {
             u.k_idx = p.k_idx;
             u.d_values = d_vals;
         }
-        u.kind = t.kind;
-        u.item_len = t.h->item_len;
-        u.d_items = t.h->items.p;
-        u.d_level0 = t.h->level0.p;
-        u.d_levels = t.h->levels.p;
-        u.capacity = t.h->cap;
-        u.fields = t.fields.empty() ? nullptr : t.fields.data();
-        u.nfields = (uint32_t)t.fields.size();
-        u.container_off = t.coff;
-        u.d_root32 = t.h->root.p;
+        tree_desc(t, u);
+    }
+    if (jr) {
+        mk_tree_set::Record& r = s->next;
+        uint64_t bytes = 0;
+        mk_tree_update jt[MK_TREES_MAX];  // the same array without the container
+        for (uint32_t i = 0; i < nt; ++i) jt[i] = table[i], jt[i].container_off = MK_NO_CONTAINER;
+        TRY(trees_journal_bytes(jt, nt, 0, &bytes));
+        TRY(journal_room(s, bytes));
+        TRY(trees_journal(false, jt, nt, nullptr, 0, nullptr, (uint8_t*)s->journal.p + s->used, bytes, st));
+        r.climbed = true;
+        r.off = s->used;
+        r.bytes = bytes;
+        r.nt = nt;
+        for (uint32_t i = 0; i < nt; ++i) r.n_old[i] = table[i].n_old, r.n_new[i] = table[i].n_new, r.k_idx[i] = table[i].k_idx;
     }
     const uint32_t clen = nparts(s) ? s->container_len : 0;
     uint64_t need = 0;
@@ -124,6 +252,7 @@ void flushed(mk_tree_set* s) {
         s->trees[i].h->count = s->pend[i].n;
     }
     s->dirty = false;
+    commit_record(s);
 }
 
 // flush, 32 bytes at d_src (looked up after the flush: a grown tree moved) to the host, one synchronise
@@ -143,6 +272,7 @@ int set_add(mk_tree_set* s, uint32_t kind, uint32_t item_len, const mk_field* fi
     if (!s || !tree) return fail(MK_EINVAL, "null pointer");
     std::lock_guard<std::mutex> lk(s->mu);
     if (s->trees.size() >= MK_TREES_MAX) return fail(MK_EINVAL, "a set holds at most %d trees", MK_TREES_MAX);
+    if (!s->cps.empty()) return fail(MK_EINVAL, "a tree added while %zu checkpoints are open", s->cps.size());
     const TreeKind* K = nullptr;
     StructTreeLayout L;
     if (kind == MK_TREE_LIST || kind == MK_TREE_BYTES) {
@@ -207,7 +337,11 @@ int set_assign(mk_tree_set* s, uint32_t tree, const uint8_t* values, uint64_t n)
     std::lock_guard<std::mutex> lk(s->mu);
     TRY(check_tree(s, tree));
     TreeHandle* h = s->trees[tree].h;
-    TRY(tree_assign(h, values, n));
+    mk_tree_set::Record rec;  // a full record: what the tree was
+    TRY(immediate_begin(s, tree, rec));
+    const int rc = tree_assign(h, values, n);
+    immediate_end(s, rec, rc);
+    if (rc) return rc;
     sp::record_assign(s->pend[tree], n, h->cap);
     s->dirty = true;
     return MK_OK;
@@ -271,7 +405,11 @@ int set_shrink(mk_tree_set* s, uint32_t tree, bool erase, const uint64_t* idx, u
         HIPCHK(hipStreamSynchronize(ctx()->stream));
         flushed(s);
     }
-    TRY(erase ? tree_erase(h, idx, k) : tree_truncate(h, n));
+    mk_tree_set::Record rec;  // a full record: what the tree was
+    TRY(immediate_begin(s, tree, rec));
+    const int rc = erase ? tree_erase(h, idx, k) : tree_truncate(h, n);
+    immediate_end(s, rec, rc);
+    if (rc) return rc;
     sp::record_assign(p, h->count, h->cap);
     s->dirty = true;  // its root in the message is the old one
     return MK_OK;
@@ -480,6 +618,8 @@ int set_copy(mk_tree_set* dst, mk_tree_set* src) {
     if (dst == src) return MK_OK;
     LockBoth lk(dst->mu, src->mu);
     TRY(sets_agree(dst, src));
+    if (!dst->cps.empty())
+        return fail(MK_EINVAL, "a copy into a set with %zu open checkpoints", dst->cps.size());
     TRY(settle(src));
     if (!src->trees.empty()) TRY(bind_set(src));
     return copy_trees(dst, src);
@@ -492,6 +632,117 @@ int set_reserve(mk_tree_set* s, uint32_t tree, uint64_t capacity) {
     TRY(tree_reserve(s->trees[tree].h, capacity));  // what is pending stays pending
     s->pend[tree].cap = s->trees[tree].h->cap;
     return MK_OK;
+}
+
+// ---- checkpoints ------------------------------------------------------------------
+int find_checkpoint(const mk_tree_set* s, uint64_t id, size_t* at) {
+    for (size_t i = 0; i < s->cps.size(); ++i)
+        if (s->cps[i].id == id) {
+            *at = i;
+            return MK_OK;
+        }
+    return fail(MK_EINVAL, "checkpoint %llu is not open", (unsigned long long)id);
+}
+
+int set_checkpoint(mk_tree_set* s, uint64_t* id) {
+    if (!s || !id) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->cps.size() >= MK_CHECKPOINTS_MAX)
+        return fail(MK_EINVAL, "%d checkpoints are open already", MK_CHECKPOINTS_MAX);
+    TRY(settle(s));  // journaled when a checkpoint is open already
+    mk_tree_set::Checkpoint c;
+    c.id = s->next_id++;
+    c.first_record = s->records.size();
+    c.used = s->used;
+    for (const auto& t : s->trees) c.counts.push_back(t.h->count);
+    c.msg = s->msg;
+    s->cps.push_back(std::move(c));
+    *id = s->cps.back().id;
+    return MK_OK;
+}
+
+// Undoes every record made since checkpoint id, newest first: a record's
+// journal restored (mk_dev_ssz_trees_restore over the trees as they are now --
+// a tree keeps the capacity it grew to), then its full copies home.  Then the
+// counts and the message of the checkpoint, and one unjournaled flush with
+// nothing dirty, which brings every tree's root into the message and the
+// message's root up to date, with the call's synchronise.
+int set_rollback(mk_tree_set* s, uint64_t id) {
+    if (!s) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    size_t at = 0;
+    TRY(find_checkpoint(s, id, &at));
+    const uint32_t nt = (uint32_t)s->trees.size();
+    if (nt) TRY(bind_set(s));
+    drop_record(s->next);
+    const mk_tree_set::Checkpoint& c = s->cps[at];
+    for (size_t r = s->records.size(); r > c.first_record; --r) {
+        mk_tree_set::Record& R = s->records[r - 1];
+        if (R.climbed) {
+            mk_tree_update table[MK_TREES_MAX] = {};
+            for (uint32_t i = 0; i < R.nt; ++i) {
+                tree_desc(s->trees[i], table[i]);
+                table[i].n_old = R.n_old[i], table[i].n_new = R.n_new[i], table[i].k_idx = R.k_idx[i];
+                table[i].container_off = MK_NO_CONTAINER;
+            }
+            TRY(trees_journal(true, table, R.nt, nullptr, 0, nullptr, (uint8_t*)s->journal.p + R.off, R.bytes,
+                              ctx()->stream));
+        }
+        for (size_t f = R.full.size(); f > 0; --f) TRY(tree_copy(s->trees[R.full[f - 1].first].h, R.full[f - 1].second));
+    }
+    for (size_t r = c.first_record; r < s->records.size(); ++r) drop_record(s->records[r]);
+    s->records.resize(c.first_record);
+    s->used = c.used;
+    for (uint32_t i = 0; i < nt; ++i) {
+        TreeHandle* h = s->trees[i].h;
+        h->count = c.counts[i];
+        sp::record_assign(s->pend[i], h->count, h->cap);  // the pending changes are dropped
+    }
+    s->msg = c.msg;
+    s->cps.resize(at);
+    if (s->cps.empty()) s->used = s->base = 0;
+    s->dirty = true;
+    if (nt) {
+        TRY(flush(s, false));
+        HIPCHK(hipStreamSynchronize(ctx()->stream));
+        flushed(s);
+    }
+    return MK_OK;
+}
+
+int set_release(mk_tree_set* s, uint64_t id) {
+    if (!s) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    size_t at = 0;
+    TRY(find_checkpoint(s, id, &at));
+    s->cps.erase(s->cps.begin(), s->cps.begin() + at + 1);
+    const size_t gone = s->cps.empty() ? s->records.size() : s->cps[0].first_record;
+    for (size_t r = 0; r < gone; ++r) drop_record(s->records[r]);
+    s->records.erase(s->records.begin(), s->records.begin() + gone);
+    for (auto& c : s->cps) c.first_record -= gone;
+    if (s->cps.empty()) {
+        drop_record(s->next);
+        s->used = s->base = 0;
+    } else {
+        s->base = s->cps[0].used;
+    }
+    return MK_OK;
+}
+
+uint64_t set_journal_bytes(const mk_tree_set* s) {
+    uint64_t b = s->used - s->base;
+    for (const auto& r : s->records)
+        for (const auto& f : r.full) b += f.second->items.cap + f.second->level0.cap + f.second->levels.cap;
+    return b;
+}
+
+int set_journal_reserve(mk_tree_set* s, uint64_t bytes) {  // bytes of live journal the buffer has room for
+    if (!s) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    const uint64_t live = s->used - s->base;
+    if (bytes <= live || s->journal.cap >= s->used + (bytes - live)) return MK_OK;
+    TRY(bind_set(s));
+    return journal_room(s, bytes - live);
 }
 
 // ---- audit ------------------------------------------------------------------------
@@ -583,6 +834,38 @@ int set_diff(mk_tree_set* a, mk_tree_set* b, mk_diff_report* reports, uint64_t* 
 
 extern "C" {
 
+int mk_tree_set_checkpoint(mk_call* call, mk_tree_set* s, uint64_t* id) {
+    Scope S(call);
+    return S.done(set_checkpoint(s, id));
+}
+
+int mk_tree_set_rollback(mk_call* call, mk_tree_set* s, uint64_t id) {
+    Scope S(call);
+    return S.done(set_rollback(s, id));
+}
+
+int mk_tree_set_release(mk_call* call, mk_tree_set* s, uint64_t id) {
+    Scope S(call, false);
+    return S.done(set_release(s, id));
+}
+
+uint64_t mk_tree_set_journal_bytes(const mk_tree_set* s) {
+    if (!s) return 0;
+    std::lock_guard<std::mutex> lk(const_cast<mk_tree_set*>(s)->mu);
+    return set_journal_bytes(s);
+}
+
+uint64_t mk_tree_set_journal_capacity(const mk_tree_set* s) {
+    if (!s) return 0;
+    std::lock_guard<std::mutex> lk(const_cast<mk_tree_set*>(s)->mu);
+    return s->journal.p ? s->journal.cap : 0;
+}
+
+int mk_tree_set_journal_reserve(mk_call* call, mk_tree_set* s, uint64_t bytes) {
+    Scope S(call);
+    return S.done(set_journal_reserve(s, bytes));
+}
+
 int mk_tree_set_diff(mk_call* call, mk_tree_set* a, mk_tree_set* b, mk_diff_report* reports, uint64_t* idx_out,
                      uint64_t max_out_per_tree) {
     Scope S(call);
@@ -634,12 +917,15 @@ int mk_tree_set_new(mk_call* call, uint32_t container_len, mk_tree_set** out) {
 void mk_tree_set_free(mk_tree_set* s) {
     if (!s) return;
     for (auto& t : s->trees) tree_free(t.h);  // each restores the caller's device
-    if (s->dev >= 0 && (s->host || s->stage.p || s->ws.p || s->croot.p)) {
+    for (auto& r : s->records)
+        for (auto& f : r.full) tree_free(f.second);
+    for (auto& f : s->next.full) tree_free(f.second);
+    if (s->dev >= 0 && (s->host || s->stage.p || s->ws.p || s->croot.p || s->journal.p)) {
         int saved = -1;
         const bool restore = hipGetDevice(&saved) == hipSuccess;
         (void)hipSetDevice(s->dev);
         if (s->host) (void)hipHostFree(s->host);
-        for (DevBuf* b : {&s->stage, &s->ws, &s->croot})
+        for (DevBuf* b : {&s->stage, &s->ws, &s->croot, &s->journal})
             if (b->p) (void)hipFree(b->p);
         if (restore) (void)hipSetDevice(saved);
     }

@@ -886,8 +886,9 @@ class TreeArgs:
         self.k_idx, self.values, self.spec, self.container_off = k_idx, values, spec, container_off
 
 
-def _tree_table(trees):
-    """The mk_tree_update array of ``trees`` (and what it points to, kept alive by the caller)."""
+def _tree_table(trees, lists: bool = True):
+    """The mk_tree_update array of ``trees`` (and what it points to, kept alive by the caller).
+    ``lists`` False: without the index arrays and the values (``trees_restore`` reads neither)."""
     from .registry import _fields
 
     arr = (_lib.TreeUpdate * max(len(trees), 1))()
@@ -895,10 +896,10 @@ def _tree_table(trees):
     for a, t in zip(arr, trees):
         if t.items.numel() * t.items.element_size() < t.n_new * t.item_len:
             raise ValueError("item buffer shorter than n_new * item_len")
-        if t.k_idx and (t.idx is None or t.idx.numel() < t.k_idx or t.idx.element_size() != 8):
+        if lists and t.k_idx and (t.idx is None or t.idx.numel() < t.k_idx or t.idx.element_size() != 8):
             raise ValueError("idx: k_idx 64-bit device indices")
         k = t.k_idx + max(t.n_new - t.n_old, 0)
-        if t.values is not None and t.values.numel() * t.values.element_size() < k * t.item_len:
+        if lists and t.values is not None and t.values.numel() * t.values.element_size() < k * t.item_len:
             raise ValueError("values shorter than (k_idx + appended) * item_len")
         if t.level0 is not None and t.level0.numel() < 32 * t.n_new:
             raise ValueError("level-0 buffer shorter than 32 * n_new")
@@ -907,9 +908,9 @@ def _tree_table(trees):
         a.d_level0 = t.level0.data_ptr() if t.level0 is not None else None
         a.d_levels = t.levels.data_ptr() if t.levels is not None else None
         a.n_old, a.n_new, a.capacity = t.n_old, t.n_new, t.capacity
-        a.d_idx = t.idx.data_ptr() if t.k_idx else None
+        a.d_idx = t.idx.data_ptr() if lists and t.k_idx else None
         a.k_idx = t.k_idx
-        a.d_values = t.values.data_ptr() if t.values is not None else None
+        a.d_values = t.values.data_ptr() if lists and t.values is not None else None
         if t.spec is not None:
             f = _fields(t.spec)
             keep.append(f)
@@ -947,6 +948,44 @@ def trees_update(trees, container: torch.Tensor = None, container_len: int = 0,
     _lib.invoke("mk_dev_ssz_trees_update", arr, len(trees), _p(container) if container_len else None, container_len,
                 _p(container_root) if container_len else None, _p(ws), ws.numel(), _stream(trees[0].items.device),
                 device=dev)
+
+
+def trees_journal_bytes(trees, container_len: int = 0) -> int:
+    """Bytes of the undo journal of one ``trees_update`` over ``trees`` (0: a list it would refuse)."""
+    arr, _keep = _tree_table(trees)
+    return _lib.load().mk_ssz_trees_journal_bytes(arr, len(trees), container_len)
+
+
+def _trees_journal_call(name, trees, container, container_len, container_root, journal):
+    if not trees:
+        raise ValueError("no trees")
+    if container_len and (container is None or container.numel() < container_len or container_root is None or
+                          container_root.numel() < 32):
+        raise ValueError("container shorter than container_len, or no 32-B container root")
+    arr, _keep = _tree_table(trees, lists=name.endswith("journal"))
+    _lib.invoke(name, arr, len(trees), _p(container) if container_len else None, container_len,
+                _p(container_root) if container_len else None, _p(journal), journal.numel() * journal.element_size(),
+                _stream(trees[0].items.device), device=_dev(trees[0].items))
+
+
+def trees_journal(trees, journal: torch.Tensor, container: torch.Tensor = None, container_len: int = 0,
+                  container_root: torch.Tensor = None) -> None:
+    """Save into ``journal`` (16-B aligned, ``trees_journal_bytes`` long) what
+    the ``trees_update`` of the same ``trees`` (and container) is about to
+    overwrite of the old state: enqueue it before that update, on the same
+    stream.  One launch, nothing hashed (mk_dev_ssz_trees_journal, DESIGN.md
+    §5r)."""
+    _trees_journal_call("mk_dev_ssz_trees_journal", trees, container, container_len, container_root, journal)
+
+
+def trees_restore(trees, journal: torch.Tensor, container: torch.Tensor = None, container_len: int = 0,
+                  container_root: torch.Tensor = None) -> None:
+    """Take the update of ``trees`` back out of the ``journal`` that
+    ``trees_journal`` filled for it: every tree is again what its ``n_old``
+    values specify, the container and its root what they were.  ``idx`` and
+    ``values`` of the trees are not read.  One launch
+    (mk_dev_ssz_trees_restore); several journals are undone newest first."""
+    _trees_journal_call("mk_dev_ssz_trees_restore", trees, container, container_len, container_root, journal)
 
 
 class TreeCopyArgs:

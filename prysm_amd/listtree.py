@@ -463,6 +463,40 @@ class TreeSet:
         """Room for ``capacity`` values in one tree; pending changes stay pending."""
         self._call("reserve", self._tree(tree), int(capacity))
 
+    # ---- checkpoints: a change taken back through an undo journal (DESIGN.md §5r)
+    def checkpoint(self) -> int:
+        """Flush what is pending and open a checkpoint; the id ``rollback`` and
+        ``release`` take.  While one is open every flush saves what it
+        overwrites (about changed x depth nodes) before it updates.  At most
+        ``_lib.MK_CHECKPOINTS_MAX`` are open at a time."""
+        cp = ctypes.c_uint64()
+        self._call("checkpoint", ctypes.byref(cp))
+        return int(cp.value)
+
+    def rollback(self, cp: int) -> None:
+        """Back to the state at checkpoint ``cp``: pending changes dropped,
+        every record since undone newest first, nothing re-hashed but the roots'
+        mix-ins and the message.  Closes ``cp`` and every later checkpoint; an
+        unknown or closed id raises and nothing changes."""
+        self._call("rollback", int(cp))
+
+    def release(self, cp: int) -> None:
+        """Forget checkpoint ``cp`` and every earlier one (the finalised case)
+        and free what only they needed."""
+        self._call("release", int(cp))
+
+    def journal_bytes(self) -> int:
+        """Bytes of HBM the open checkpoints hold."""
+        return int(_lib.load().mk_tree_set_journal_bytes(self._handle))
+
+    def journal_capacity(self) -> int:
+        """Bytes allocated for the journals (what ``release`` frees is used again before this grows)."""
+        return int(_lib.load().mk_tree_set_journal_capacity(self._handle))
+
+    def journal_reserve(self, nbytes: int) -> None:
+        """Room for ``nbytes`` of journal, so that no flush of a slot grows it."""
+        self._call("journal_reserve", int(nbytes))
+
     def audit(self):
         """Is every tree what its values say, and the message what the trees
         say?  Whatever is pending is flushed first, as ``root()`` does; then
