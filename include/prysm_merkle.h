@@ -1214,6 +1214,73 @@ uint64_t mk_merkle_root_workspace_bytes(uint64_t n);
 int mk_dev_merkle_root(mk_call* call, const void* d_data, const uint64_t* d_offs, uint64_t n, uint32_t fixed_len,
                        void* d_heap, uint64_t heap_bytes, void* d_leaves32, void* d_out32, void* stream);
 
+/* ---- hashutil.RepeatHash (hash.go:29-34): chains, hash onions, the RANDAO check ---- */
+/* RepeatHash(x, k) is Keccak-256 applied k times to a 32-byte value; k == 0 returns x.  One chain is serial; its
+ * callers are not: verifyBlockRandao (block_operations.go:109-123) runs one chain per block, the hash onions
+ * (chaintest/backend/helpers.go:125-135) one per validator with every layer kept.  A chain never leaves the
+ * registers of the lane or wave that runs it.
+ *
+ * Layer counts are data (RandaoLayers comes from a proposer's record), so every entry takes max_layers, the most
+ * permutations a chain of this call may run, and MK_EINVAL answers max_layers > MK_REPEAT_MAX_LAYERS.  Nothing a
+ * caller passes makes a kernel run more than max_layers permutations per chain.
+ *
+ * form: MK_REPEAT_LANE runs one chain per GPU lane (a wave runs for as long as its longest chain; shorter ones
+ * wait masked off), MK_REPEAT_WAVE one chain per wave (for few chains: 2.8 against 8.7-10 us per layer of a lone chain),
+ * MK_REPEAT_AUTO picks by the number of chains.  The results are the same bit for bit; the forced forms exist
+ * for tests and timing.  The host entries use MK_REPEAT_AUTO.
+ *
+ * Device pointers may have any alignment; 16-B aligned seeds and outputs (and, for a verify, records, stride and
+ * offsets that are multiples of 4) take whole-word accesses, anything else goes byte by byte.  n == 0 (m == 0) is
+ * MK_OK and launches nothing; n, m < 2^31. */
+#define MK_REPEAT_MAX_LAYERS (1u << 20)
+#define MK_REPEAT_AUTO 0u
+#define MK_REPEAT_LANE 1u
+#define MK_REPEAT_WAVE 2u
+/* the verdict bytes of a verify */
+#define MK_REPEAT_BAD 0       /* the chain's end is not the commitment */
+#define MK_REPEAT_OK 1        /* RepeatHash(reveal, layers) == commitment */
+#define MK_REPEAT_TOO_DEEP 2  /* the record's 64-bit layer count exceeds max_layers: the chain was not run */
+#define MK_REPEAT_NO_RECORD 3 /* idx >= n_records (device entry only: the host entries refuse the call) */
+/* chain: d_out[i] = RepeatHash(d_seeds[i], d_layers[i]) (n x 32 bytes each, d_layers n x u32).  The host cannot
+ * see d_layers: a chain whose count exceeds max_layers gets 32 zero bytes and sets bit 0 of *d_status (one u32
+ * of the caller's workspace, 4-B aligned); the other chains are unaffected.  The call only ever sets the word:
+ * the caller clears it once and may check it after any number of calls (a clear per call would be a second
+ * stream operation beside a launch of a few microseconds). */
+int mk_dev_repeat_hash(mk_call* call, const void* d_seeds, const uint32_t* d_layers, uint64_t n, uint32_t max_layers,
+                       uint32_t form, void* d_out, uint32_t* d_status, void* stream);
+/* onion: d_out[i][t] = RepeatHash(d_seeds[i], t), t = 0 .. layers: n x (layers + 1) x 32 bytes, row 0 the seed,
+ * each row stored as its layer completes.  layers <= MK_REPEAT_MAX_LAYERS. */
+int mk_dev_hash_onion(mk_call* call, const void* d_seeds, uint64_t n, uint32_t layers, uint32_t form, void* d_out,
+                      void* stream);
+/* verify: for proposal j, rec = d_records + d_idx[j] * stride, d_ok[j] (one byte) = MK_REPEAT_OK when
+ * RepeatHash(d_reveals[j], le64(rec + layers_off)) == rec[commit_off, commit_off + 32), else one of the codes
+ * above.  The layer count is compared as 64 bits.  commit_off + 32 and layers_off + 8 <= stride.  Indices may
+ * repeat.  For the 160-B ValidatorRecord: stride 160, commit_off 80, layers_off 112. */
+int mk_dev_verify_repeat_hash(mk_call* call, const void* d_records, uint64_t n_records, uint64_t stride,
+                              uint32_t commit_off, uint32_t layers_off, const uint64_t* d_idx, const void* d_reveals,
+                              uint64_t m, uint32_t max_layers, uint32_t form, uint8_t* d_ok, void* stream);
+/* The same on host buffers (upload, one launch, read-back).  A layers[i] > max_layers is MK_EINVAL naming the
+ * first such i, with nothing launched and `out` untouched; so is an idx[j] >= n_records. */
+int mk_repeat_hash_batch(mk_call* call, const uint8_t* seeds, const uint32_t* layers, uint64_t n, uint32_t max_layers,
+                         uint8_t* out);
+/* RepeatHash itself; num_times > MK_REPEAT_MAX_LAYERS is MK_EINVAL. */
+int mk_repeat_hash(mk_call* call, const uint8_t data[32], uint64_t num_times, uint8_t out[32]);
+int mk_hash_onion(mk_call* call, const uint8_t* seeds, uint64_t n, uint32_t layers, uint8_t* out);
+int mk_verify_repeat_hash(mk_call* call, const uint8_t* records, uint64_t n_records, uint64_t stride,
+                          uint32_t commit_off, uint32_t layers_off, const uint64_t* idx, const uint8_t* reveals,
+                          uint64_t m, uint32_t max_layers, uint8_t* ok);
+/* The verify against the records a resident registry tree owns: only idx and the reveals go up and the m
+ * verdicts come back; no record is read back.  Read-only (root, levels and records stay as they are).  idx[j] >=
+ * the tree's count, commit_off + 32 or layers_off + 8 > the record length are MK_EINVAL with nothing launched.
+ * The set's form takes tree number `tree`, which must be an MK_TREE_STRUCT tree, and flushes pending changes
+ * first, as mk_tree_set_branches does: a pending update is seen. */
+int mk_struct_list_tree_verify_repeat_hash(mk_call* call, mk_struct_list_tree* t, uint32_t commit_off,
+                                           uint32_t layers_off, const uint64_t* idx, const uint8_t* reveals,
+                                           uint64_t m, uint32_t max_layers, uint8_t* ok);
+int mk_tree_set_verify_repeat_hash(mk_call* call, mk_tree_set* s, uint32_t tree, uint32_t commit_off,
+                                   uint32_t layers_off, const uint64_t* idx, const uint8_t* reveals, uint64_t m,
+                                   uint32_t max_layers, uint8_t* ok);
+
 /* ---- trieutil deposit trie (deposit_trie.go:29-81) ---------------------- */
 /* Level array of a depth-`depth` trie with room for `capacity` leaves: level
  * d (d = 0: leaf hashes Hash(deposit)) starts at node

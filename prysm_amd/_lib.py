@@ -244,6 +244,15 @@ _SIGS = {
     "mk_struct_list_tree_diff": (_int, [_cp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "mk_bytes_list_tree_diff": (_int, [_cp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "mk_tree_set_diff": (_int, [_cp, _vp, _vp, _vp, _vp, _u64]),
+    "mk_dev_repeat_hash": (_int, [_cp, _vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp]),
+    "mk_dev_hash_onion": (_int, [_cp, _vp, _u64, _u32, _u32, _vp, _vp]),
+    "mk_dev_verify_repeat_hash": (_int, [_cp, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
+    "mk_repeat_hash_batch": (_int, [_cp, _vp, _vp, _u64, _u32, _vp]),
+    "mk_repeat_hash": (_int, [_cp, _vp, _u64, _vp]),
+    "mk_hash_onion": (_int, [_cp, _vp, _u64, _u32, _vp]),
+    "mk_verify_repeat_hash": (_int, [_cp, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _u64, _u32, _vp]),
+    "mk_struct_list_tree_verify_repeat_hash": (_int, [_cp, _vp, _u32, _u32, _vp, _vp, _u64, _u32, _vp]),
+    "mk_tree_set_verify_repeat_hash": (_int, [_cp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _u32, _vp]),
     "mk_verify_merkle_branches":(_int, [_cp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "mk_dev_synth_fill": (_int, [_cp, _vp, _u64, _u64, _u64, _vp]),
     "mk_prof_enable": (_int, [_int]),
@@ -269,6 +278,10 @@ MK_TREES_MAX = 16
 MK_NO_CONTAINER = 0xFFFFFFFF
 MK_CONTAINER_MAX = 4096
 MK_CHECKPOINTS_MAX = 64
+# hashutil.RepeatHash in batches: the cap on any call's max_layers, the kernel forms, the verdicts
+MK_REPEAT_MAX_LAYERS = 1 << 20
+MK_REPEAT_AUTO, MK_REPEAT_LANE, MK_REPEAT_WAVE = 0, 1, 2
+MK_REPEAT_BAD, MK_REPEAT_OK, MK_REPEAT_TOO_DEEP, MK_REPEAT_NO_RECORD = 0, 1, 2, 3
 # the dirty share from which a resident tree's host handle rebuilds instead of climbing: count / DIV
 # (MK_*_TREE_REBUILD_DIV in csrc/list_tree_api.cpp, struct_tree_api.cpp, bytes_tree_api.cpp)
 LIST_TREE_REBUILD_DIV = 512

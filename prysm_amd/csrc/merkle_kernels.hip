@@ -4144,3 +4144,5 @@ __global__ __launch_bounds__(256) void k_many_final(const uint8_t* __restrict__ 
 #include "kernels_trie_admin.hip"
 // records with list fields; k_struct_nested's column helpers
 #include "kernels_struct_list.hip"
+// hashutil.RepeatHash in batches: chains, onions, the RANDAO check
+#include "kernels_repeat.hip"

@@ -388,4 +388,28 @@ __global__ void k_trie_audit(const uint4* levels, uint64_t cap, uint64_t count, 
 __global__ void k_trie_copy(const uint4* src, uint64_t cap_src, uint64_t count, uint4* dst, uint64_t cap_dst,
                             uint32_t depth, const uint4* src_root, uint4* dst_root);
 
+// hashutil.RepeatHash in batches (kernels_repeat.hip, repeat_api.cpp; the helpers: repeat_dev.hpp).
+enum RepeatMode : int { kRepeatChain = 0, kRepeatOnion = 1, kRepeatVerify = 2 };
+struct RepeatArgs {
+    const uint8_t* seeds;    // n x 32: the seeds, verify: the reveals
+    const uint32_t* layers;  // chain: n trip counts
+    uint8_t* out;            // chain: n x 32; onion: n x (max_layers + 1) x 32; verify: n verdict bytes
+    uint32_t* status;        // chain: set to 1 when a trip count exceeds max_layers (NULL: the host checked)
+    const uint8_t* records;  // verify: n_records records `stride` bytes apart
+    const uint64_t* idx;     // verify: n record indices
+    uint64_t n, n_records, stride;
+    uint32_t commit_off, layers_off;  // verify: the 32-B commitment and the le64 layer count inside a record
+    uint32_t max_layers;              // the bound of every chain's trip count; onion: the trip count
+    uint32_t io16;   // seeds and (chain, onion) out are 16-B aligned: whole-word accesses, else bytes
+    uint32_t rec4;   // verify: records, stride and both offsets are multiples of 4: dword loads, else bytes
+};
+constexpr uint32_t kRepeatThreads = 256;
+constexpr uint32_t kRepeatWaves = kRepeatThreads / 64;  // k_repeat_wave: chains per workgroup
+// one chain per GPU lane; a wave runs as long as its longest chain, the shorter ones masked off
+template <int MODE>
+__global__ void k_repeat_lane(RepeatArgs a);
+// one chain per wave (mk::spread), kRepeatWaves chains per workgroup
+template <int MODE>
+__global__ void k_repeat_wave(RepeatArgs a);
+
 }  // namespace mk

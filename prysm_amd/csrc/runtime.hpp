@@ -137,6 +137,18 @@ int dev_hash_batch(const void* d_in, uint64_t n, uint32_t msg_len, void* d_out, 
 int dev_hash_var(const void* d_in, const uint64_t* d_offs, uint64_t n, void* d_out, hipStream_t st);
 int64_t uniform_len(const uint64_t* offs, uint64_t n);  // uniform message length of offs[0..n] (relative), or -1
 
+// ---- RepeatHash in batches (repeat_api.cpp) ------------------------------
+// the argument rules every entry shares (no device needed): the cap, the form and the size of one launch; the two
+// fields inside `stride` bytes (`what` names it in the message); every index below `count`
+int repeat_check_call(uint64_t n, uint32_t max_layers, uint32_t form);
+int repeat_check_offsets(uint64_t stride, uint32_t commit_off, uint32_t layers_off, const char* what);
+int repeat_check_indices(const uint64_t* idx, uint64_t m, uint64_t count, const char* noun);
+// the verify against the records a registry tree's handle owns (MK_TREE_STRUCT only): idx and the reveals up,
+// one launch, the m verdicts back.  Takes t's lock; read-only.
+struct TreeHandle;
+int tree_verify_repeat_hash(TreeHandle* t, uint32_t commit_off, uint32_t layers_off, const uint64_t* idx,
+                            const uint8_t* reveals, uint64_t m, uint32_t max_layers, uint8_t* ok);
+
 // ---- merkleHash (merkle_api.cpp) -------------------------------------------------
 inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
 int launch_plan(const Plan& p, const uint8_t* d_items, uint8_t* d_out32, uint8_t* d_ws, uint64_t ws_bytes,

@@ -354,6 +354,13 @@ int mk_struct_list_tree_branches(mk_call* call, mk_struct_list_tree* t, const ui
     return S.done(tree_branches(t, idx, k, values_out, branches_out));
 }
 
+int mk_struct_list_tree_verify_repeat_hash(mk_call* call, mk_struct_list_tree* t, uint32_t commit_off,
+                                           uint32_t layers_off, const uint64_t* idx, const uint8_t* reveals,
+                                           uint64_t m, uint32_t max_layers, uint8_t* ok) {
+    Scope S(call);
+    return S.done(tree_verify_repeat_hash(t, commit_off, layers_off, idx, reveals, m, max_layers, ok));
+}
+
 int mk_struct_list_tree_clone(mk_call* call, mk_struct_list_tree* src, mk_struct_list_tree** out) {
     Scope S(call);
     TreeHandle* t = nullptr;

@@ -484,6 +484,30 @@ int set_branches(mk_tree_set* s, uint32_t tree, const uint64_t* idx, uint64_t k,
     return MK_OK;
 }
 
+// RepeatHash(reveal, layers) == commitment against the records of registry tree `tree`: what
+// is pending goes to the device first, as for set_branches; then the handle's own verify.  Read-only.
+int set_verify_repeat_hash(mk_tree_set* s, uint32_t tree, uint32_t commit_off, uint32_t layers_off,
+                           const uint64_t* idx, const uint8_t* reveals, uint64_t m, uint32_t max_layers, uint8_t* ok) {
+    if (!s || (m && (!idx || !reveals || !ok))) return fail(MK_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    TRY(check_tree(s, tree));
+    TreeHandle* h = s->trees[tree].h;
+    if (s->trees[tree].kind != MK_TREE_STRUCT)
+        return fail(MK_EINVAL, "tree %u is a %s: the verify takes a struct list tree", tree, h->kind->name);
+    // against the pending count, before anything is flushed; the handle's verify checks the rest
+    TRY(repeat_check_indices(idx, m, s->pend[tree].count(), h->kind->noun));
+    TRY(repeat_check_offsets(h->item_len, commit_off, layers_off, "record length"));
+    TRY(repeat_check_call(m, max_layers, MK_REPEAT_AUTO));
+    if (m == 0) return MK_OK;
+    TRY(bind_set(s));
+    if (s->dirty) {
+        TRY(flush(s));
+        HIPCHK(hipStreamSynchronize(ctx()->stream));
+        flushed(s);
+    }
+    return tree_verify_repeat_hash(h, commit_off, layers_off, idx, reveals, m, max_layers, ok);
+}
+
 // ---- clone, copy, reserve ---------------------------------------------------------
 // everything pending onto the device and waited for: the handles hold what root() would describe
 int settle(mk_tree_set* s) {
@@ -994,6 +1018,13 @@ int mk_tree_set_branches(mk_call* call, mk_tree_set* s, uint32_t tree, const uin
                          uint8_t* values_out, uint8_t* branches_out, uint8_t* container_out) {
     Scope S(call);
     return S.done(set_branches(s, tree, idx, k, values_out, branches_out, container_out));
+}
+
+int mk_tree_set_verify_repeat_hash(mk_call* call, mk_tree_set* s, uint32_t tree, uint32_t commit_off,
+                                   uint32_t layers_off, const uint64_t* idx, const uint8_t* reveals, uint64_t m,
+                                   uint32_t max_layers, uint8_t* ok) {
+    Scope S(call);
+    return S.done(set_verify_repeat_hash(s, tree, commit_off, layers_off, idx, reveals, m, max_layers, ok));
 }
 
 }  // extern "C"

@@ -408,6 +408,91 @@ def hash_batch(msgs: torch.Tensor, n: int, msg_len: int, out: torch.Tensor = Non
     return out
 
 
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _same_dev(dev: int, **tensors) -> None:
+    """Every tensor given (None: absent) lies on GPU ``dev``: a kernel must not be handed a pointer of
+    another device or of the host."""
+    for name, t in tensors.items():
+        if t is not None and _dev(t) != dev:
+            raise ValueError(f"{name} is on {t.device}, not on cuda:{dev}")
+
+
+def repeat_hash(seeds: torch.Tensor, layers: torch.Tensor, n: int, max_layers: int,
+                form: int = _lib.MK_REPEAT_AUTO, out: torch.Tensor = None, status: torch.Tensor = None):
+    """``out[i] = RepeatHash(seeds[i], layers[i])`` for n chains resident on the
+    device (hashutil.RepeatHash, hash.go:29-34): ``seeds`` n x 32
+    bytes, ``layers`` n 32-bit counts.  Returns ``(out, status)``: the host
+    cannot see the counts, so a chain whose count exceeds ``max_layers`` gets 32
+    zero bytes and sets the one-word ``status`` tensor (int32) to 1.  A
+    ``status`` passed in is only ever set, never cleared: clear it once, check
+    it after any number of calls; without one the call makes a zeroed word."""
+    dev = _dev(seeds)
+    _same_dev(dev, layers=layers, out=out, status=status)
+    if _nbytes(seeds) < 32 * n:
+        raise ValueError("seeds shorter than n x 32 bytes")
+    if layers.element_size() != 4 or layers.numel() < n:
+        raise ValueError("layers: at least n 32-bit integers")
+    if out is None:
+        out = torch.empty(n * 32, dtype=torch.uint8, device=seeds.device)
+    elif _nbytes(out) < 32 * n:
+        raise ValueError("out shorter than n x 32 bytes")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=seeds.device)
+    elif status.element_size() != 4 or status.numel() < 1:
+        raise ValueError("status: one 32-bit word")
+    _lib.invoke("mk_dev_repeat_hash", _p(seeds), _p(layers), n, max_layers, form, _p(out), _p(status),
+                _stream(seeds.device), device=dev)
+    return out, status
+
+
+def hash_onion(seeds: torch.Tensor, n: int, layers: int, form: int = _lib.MK_REPEAT_AUTO,
+               out: torch.Tensor = None) -> torch.Tensor:
+    """The hash onions of n seeds resident on the device, every layer kept:
+    n x (layers + 1) x 32 bytes, ``out[i][t] = RepeatHash(seeds[i], t)``, row 0
+    the seed (mk_dev_hash_onion)."""
+    dev = _dev(seeds)
+    _same_dev(dev, out=out)
+    if _nbytes(seeds) < 32 * n:
+        raise ValueError("seeds shorter than n x 32 bytes")
+    if layers < 0:
+        raise ValueError("layers < 0")
+    if out is None:
+        out = torch.empty(n * (layers + 1) * 32, dtype=torch.uint8, device=seeds.device)
+    elif _nbytes(out) < n * (layers + 1) * 32:
+        raise ValueError("out shorter than n x (layers + 1) x 32 bytes")
+    _lib.invoke("mk_dev_hash_onion", _p(seeds), n, layers, form, _p(out), _stream(seeds.device), device=dev)
+    return out
+
+
+def verify_repeat_hash(records: torch.Tensor, n_records: int, stride: int, commit_off: int, layers_off: int,
+                       indices: torch.Tensor, reveals: torch.Tensor, m: int, max_layers: int,
+                       form: int = _lib.MK_REPEAT_AUTO, out: torch.Tensor = None) -> torch.Tensor:
+    """verifyBlockRandao (block_operations.go:109-123) for m proposals against
+    records resident on the device: (m,) uint8, ``MK_REPEAT_OK`` where
+    ``RepeatHash(reveals[j], le64(rec + layers_off)) == rec[commit_off:+32]``,
+    rec = record ``indices[j]``; ``MK_REPEAT_BAD`` where not; ``MK_REPEAT_TOO_DEEP``
+    where the record's 64-bit layer count exceeds ``max_layers`` (the chain is
+    not run); ``MK_REPEAT_NO_RECORD`` where ``indices[j] >= n_records``."""
+    dev = _dev(reveals)
+    _same_dev(dev, records=records, indices=indices, out=out)
+    if _nbytes(records) < n_records * stride:
+        raise ValueError("records shorter than n_records x stride bytes")
+    if indices.element_size() != 8 or indices.numel() < m:
+        raise ValueError("indices: at least m 64-bit integers")
+    if _nbytes(reveals) < 32 * m:
+        raise ValueError("reveals shorter than m x 32 bytes")
+    if out is None:
+        out = torch.empty(m, dtype=torch.uint8, device=reveals.device)
+    elif _nbytes(out) < m:
+        raise ValueError("out shorter than m bytes")
+    _lib.invoke("mk_dev_verify_repeat_hash", _p(records), n_records, stride, commit_off, layers_off, _p(indices),
+                _p(reveals), m, max_layers, form, _p(out), _stream(reveals.device), device=dev)
+    return out
+
+
 def deposit_trie_levels_bytes(capacity: int, depth: int) -> int:
     return _lib.load().mk_deposit_trie_levels_bytes(capacity, depth)
 

@@ -1,7 +1,7 @@
 """Host mirror of ``shared/hashutil`` over the HIP engine.
 
-Reference: shared/hashutil/hash.go:11-25 (``Hash``), merkleRoot.go:12-30
-(``MerkleRoot``).  Same names, argument meaning and return values; the
+Reference: shared/hashutil/hash.go:11-25 (``Hash``), hash.go:29-34
+(``RepeatHash``), merkleRoot.go:12-30 (``MerkleRoot``).  Same names, argument meaning and return values; the
 batched entry points are the new API the north star asks for (the reference
 has no batch form).  Every digest is computed on the GPU; there is no CPU
 fallback.
@@ -58,6 +58,54 @@ def hash_batch_var(msgs: Sequence[bytes]) -> List[bytes]:
     out = np.empty((len(msgs), 32), dtype=np.uint8)
     _lib.invoke("mk_hash_batch_var", _ptr(data), _ptr(offs), len(msgs), _ptr(out))
     return [bytes(r) for r in out]
+
+
+def RepeatHash(data: bytes, num_times: int) -> bytes:
+    """hashutil.RepeatHash (hash.go:29-34): Keccak-256 applied ``num_times``
+    times to the 32-byte ``data``; 0 returns ``data``.  ``num_times`` above
+    ``_lib.MK_REPEAT_MAX_LAYERS`` raises."""
+    data = bytes(data)
+    if len(data) != 32:
+        raise ValueError("RepeatHash takes a [32]byte")
+    if num_times < 0:
+        raise ValueError("num_times is a uint64")
+    out = ctypes.create_string_buffer(32)
+    _lib.invoke("mk_repeat_hash", ctypes.create_string_buffer(data, 32), int(num_times), out)
+    return out.raw
+
+
+def _seeds(seeds) -> np.ndarray:
+    a = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1)
+    if a.size % 32:
+        raise ValueError(f"{a.size} bytes are not a whole number of 32-byte seeds")
+    return a
+
+
+def repeat_hash_batch(seeds, layers, max_layers: int = _lib.MK_REPEAT_MAX_LAYERS) -> np.ndarray:
+    """``out[i] = RepeatHash(seeds[i], layers[i])`` for n chains in one launch:
+    (n, 32) uint8.  ``seeds``: n * 32 bytes (any shape); ``layers``: n counts, or
+    one for all.  A count above ``max_layers`` raises with nothing launched
+    (layer counts are data: the caller states the most it will pay for)."""
+    a = _seeds(seeds)
+    n = a.size // 32
+    lay = np.ascontiguousarray(np.broadcast_to(np.asarray(layers, dtype=np.uint64).reshape(-1), (n,)))
+    if lay.size and int(lay.max()) > 0xFFFFFFFF:
+        raise _lib.MerkleError(_lib.MK_EINVAL, f"a layer count of {int(lay.max())} is above any max_layers")
+    lay = lay.astype(np.uint32)
+    out = np.empty((n, 32), dtype=np.uint8)
+    _lib.invoke("mk_repeat_hash_batch", _ptr(a), _ptr(lay), n, int(max_layers), _ptr(out))
+    return out
+
+
+def hash_onion(seeds, layers: int) -> np.ndarray:
+    """The hash onions of n seeds (chaintest/backend/helpers.go:125-135) with
+    every layer kept: (n, layers + 1, 32) uint8, ``out[i][t] =
+    RepeatHash(seeds[i], t)``, row 0 the seed."""
+    a = _seeds(seeds)
+    n = a.size // 32
+    out = np.empty((n, int(layers) + 1, 32), dtype=np.uint8)
+    _lib.invoke("mk_hash_onion", _ptr(a), n, int(layers), _ptr(out))
+    return out
 
 
 def MerkleRoot(values: List[bytes]) -> bytes:

@@ -253,6 +253,18 @@ def verify_branches(values, indices, n: int, item_len: int, branches, root, cont
     return ok.astype(bool)
 
 
+def _verify_repeat_hash(call, head, indices, reveals, commit_off, layers_off, max_layers) -> np.ndarray:
+    """What StructListTree.verify_repeat_hash and TreeSet.verify_repeat_hash share."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    rev = np.ascontiguousarray(reveals, dtype=np.uint8).reshape(-1)
+    if rev.size != 32 * idx.size:
+        raise ValueError("one 32-byte reveal per index")
+    ok = np.zeros(idx.size, dtype=np.uint8)
+    call("verify_repeat_hash", *head, int(commit_off), int(layers_off), _ptr(idx), _ptr(rev), idx.size,
+         int(max_layers), _ptr(ok))
+    return ok
+
+
 class ListTree(_Tree):
     """A list of fixed-length items and its merkleHash tree, device-resident."""
 
@@ -282,6 +294,18 @@ class StructListTree(_Tree):
 
     def _bytes(self, records) -> np.ndarray:  # a structured array as its bytes: no dtype conversion
         return np.ascontiguousarray(records).view(np.uint8)
+
+    def verify_repeat_hash(self, indices, reveals, commit_off: int, layers_off: int,
+                           max_layers: int = _lib.MK_REPEAT_MAX_LAYERS) -> np.ndarray:
+        """verifyBlockRandao (block_operations.go:109-123) for m proposals
+        against the records the tree holds on the device: (m,) uint8, 1 where
+        ``RepeatHash(reveals[j], le64(rec[layers_off:+8])) ==
+        rec[commit_off:+32]`` for record ``indices[j]``, 0 where not, 2 where
+        the record's 64-bit layer count exceeds ``max_layers`` (the chain is not
+        run).  Only the indices and the reveals go up and m bytes come back; the
+        tree is not changed.  An index >= len(self) or an offset past the record
+        raises."""
+        return _verify_repeat_hash(self._call, (), indices, reveals, commit_off, layers_off, max_layers)
 
 
 class BytesListTree(_Tree):
@@ -567,3 +591,12 @@ class TreeSet:
         msg = np.zeros(self.container_len, dtype=np.uint8)
         self._call("branches", tree, _ptr(idx), idx.size, _ptr(values), _ptr(out), _ptr(msg))
         return values, out, msg.tobytes()
+
+    def verify_repeat_hash(self, tree, indices, reveals, commit_off: int, layers_off: int,
+                           max_layers: int = _lib.MK_REPEAT_MAX_LAYERS) -> np.ndarray:
+        """``StructListTree.verify_repeat_hash`` against the records of one
+        ``MK_TREE_STRUCT`` tree of the set (any other kind raises), whatever is
+        pending flushed first as ``root()`` does: an update not yet flushed is
+        seen."""
+        return _verify_repeat_hash(self._call, (self._tree(tree),), indices, reveals, commit_off, layers_off,
+                                   max_layers)

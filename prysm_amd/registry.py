@@ -36,6 +36,9 @@ VALIDATOR_DTYPE = np.dtype([
     ("status_flags", "<u8"),
 ])
 assert VALIDATOR_DTYPE.itemsize == 160
+# where verifyBlockRandao's two fields lie in a record (block_operations.go:109-123): bytes 80..112 and 112..120
+RANDAO_COMMITMENT_OFF = VALIDATOR_DTYPE.fields["randao_commitment_hash32"][1]
+RANDAO_LAYERS_OFF = VALIDATOR_DTYPE.fields["randao_layers"][1]
 
 # (kind, offset, len) in declaration order
 VALIDATOR_FIELDS = [(_lib.MK_FIELD_BYTES, 0, 48), (_lib.MK_FIELD_BYTES, 48, 32), (_lib.MK_FIELD_BYTES, 80, 32)] + \

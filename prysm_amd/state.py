@@ -883,6 +883,17 @@ class BeaconTreeSet(TreeSet):
         ``root()`` with the block's state root, keep it or drop it."""
         return super().clone()
 
+    def verify_randao(self, proposer_indices, reveals, max_layers: int = _lib.MK_REPEAT_MAX_LAYERS) -> np.ndarray:
+        """verifyBlockRandao (block_operations.go:109-123) for a batch of blocks
+        against the resident registry: verdict j is 1 where
+        ``RepeatHash(reveals[j], proposer.RandaoLayers) ==
+        proposer.RandaoCommitmentHash32`` for validator ``proposer_indices[j]``,
+        0 where not, 2 where RandaoLayers exceeds ``max_layers``
+        (``TreeSet.verify_repeat_hash`` with the ValidatorRecord's offsets; no
+        record is read back, pending registry updates are seen)."""
+        return self.verify_repeat_hash("registry", proposer_indices, reveals, R.RANDAO_COMMITMENT_OFF,
+                                       R.RANDAO_LAYERS_OFF, max_layers)
+
     def assign_state(self, state: BeaconState) -> None:
         """Every small field put, every list assigned from ``state``."""
         for name in _SCALARS:
