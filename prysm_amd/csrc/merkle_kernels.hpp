@@ -41,7 +41,7 @@ template <uint32_t NT>
 __global__ void k_struct_list(const uint8_t* rec, uint64_t n, ListSpec ls, uint4* roots);
 template <int NB, int NRAW>
 __global__ void k_struct_reg(const uint8_t* rec, uint64_t n, StructSpec sp, uint32_t vec16, uint4* roots);
-// validator layout (kValOff/kValLen in merkle_kernels.hip), any n (a partial last group);
+// validator layout (kValOff/kValLen in kernels_struct.hip), any n (a partial last group);
 // gpw > 0: contiguous groups per workgroup plus the level-1 windows of the roots' merkleHash
 // (and of a second list of vbytes bytes at vals, when vals != nullptr)
 // PREV (a stream of states, gpw == 4): the same launch also builds levels

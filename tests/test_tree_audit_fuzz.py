@@ -49,7 +49,7 @@ def test_arithmetic_has_no_hip_and_is_the_kernels():
     for fn in ("audit_shape(", "audit_slot_first(", "audit_slot_child(", "audit_slot_node(", "audit_item_in("):
         assert fn in audit, fn
     assert "g_arrive" not in audit
-    assert "g_arrive" not in kern  # the arrival counters stay with the fused tops (merkle_kernels.hip)
+    assert "g_arrive" not in kern  # the arrival counters stay with the fused tops (kernels_top.hip)
     with open(os.path.join(CSRC, "tree_audit_api.cpp")) as f:
         host = f.read()
     assert '#include "tree_audit.hpp"' in host and "audit_items(" in host and "audit_shape(" in host

@@ -62,3 +62,31 @@ def test_rules_have_no_hip_and_are_the_kernels():
     assert '#include "trie_admin.hpp"' in fuzz
     for fn in ("ta_truncate(", "ta_fork_point(", "ta_audit(", "ta_copy_first("):
         assert fn in fuzz, fn
+
+
+def test_every_kernel_file_is_a_part_of_the_one_unit():
+    """The kernel files and the Makefile agree: what merkle_kernels.hip includes is KERNEL_PARTS, in the same
+    order, every kernels_*.hip on disk is among them, none is an object of its own, and each refuses to compile
+    outside the unit."""
+    with open(os.path.join(CSRC, "merkle_kernels.hip")) as f:
+        unit = f.read()
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        mk = f.read()
+    parts = re.search(r"^KERNEL_PARTS := (.*)$", mk, re.M).group(1).split()
+    objs = re.search(r"^OBJS := (.*)$", mk, re.M).group(1)
+    included = re.findall(r'^#include "(kernels_\w+\.hip)"$', unit, re.M)
+    assert len(set(parts)) == len(parts)
+    assert included == parts
+    assert sorted(parts) == sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and f != "merkle_kernels.hip")
+    assert unit.index("#define MK_KERNEL_UNIT 1") < unit.index("#include ")  # ahead of the first include
+    for part in parts:
+        assert part[:-4] not in objs, part
+        with open(os.path.join(CSRC, part)) as f:
+            src = f.read()
+        guard = '#ifndef MK_KERNEL_UNIT\n#error "%s is built through merkle_kernels.hip"\n#endif\n' % part
+        assert guard in src and "__global__" not in src[:src.index(guard)], part
+        assert "#define MK_KERNEL_UNIT" not in src, part
+    assert "g_arrive" not in unit  # the arrival counters stay in the one file that defines them
+    for part in parts:
+        with open(os.path.join(CSRC, part)) as f:
+            assert ("g_arrive" in f.read()) == (part == "kernels_top.hip"), part

@@ -3,12 +3,16 @@
 metadata note.
 
     python tools/kernel_resources.py [--match SUBSTR] [--compare profiles/kernel_split/resources.json] [--out FILE]
+    python tools/kernel_resources.py --text-sha256 [--lib prysm_amd/lib/merkle_kernels.o]
 
 Unbundles the gfx950 code object from prysm_amd/lib/libprysm_merkle.so with
 clang-offload-bundler and parses `llvm-readelf --notes`.  --compare checks
 every kernel that both sides name (after --match) for equal figures and exits
-1 when one differs."""
+1 when one differs.  --text-sha256 prints one line, the sha256 of the code
+object's .text: a move of kernel source that is a pure cut leaves it as it was
+(profiles/kernel_split/text_identity.json)."""
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -22,15 +26,29 @@ KEYS = {".vgpr_count": "vgpr_count", ".sgpr_count": "sgpr_count", ".private_segm
         ".group_segment_fixed_size": "group_segment_fixed_size"}
 
 
+def code_object(lib, tmp):
+    """The gfx950 code object of a library or an object file, unbundled into the directory tmp."""
+    co, fat = os.path.join(tmp, "gfx950.co"), os.path.join(tmp, "lib.hipfb")
+    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat],
+                   check=True)
+    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+    return co
+
+
+def text_sha256(lib):
+    with tempfile.TemporaryDirectory() as tmp:
+        text = os.path.join(tmp, "text.bin")
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.text",
+                        code_object(lib, tmp), text], check=True)
+        with open(text, "rb") as f:
+            return hashlib.sha256(f.read()).hexdigest()
+
+
 def kernel_resources(lib):
     with tempfile.TemporaryDirectory() as tmp:
-        co, fat = os.path.join(tmp, "gfx950.co"), os.path.join(tmp, "lib.hipfb")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat],
-                       check=True)
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", code_object(lib, tmp)], check=True,
+                               capture_output=True, text=True).stdout
     out, cur = {}, None
     for line in notes.splitlines():
         m = re.match(r"\s*-?\s*(\.[a-z_]+):\s*(.*)$", line)
@@ -52,7 +70,11 @@ def main():
     ap.add_argument("--match", default="")
     ap.add_argument("--compare")
     ap.add_argument("--out")
+    ap.add_argument("--text-sha256", action="store_true")
     a = ap.parse_args()
+    if a.text_sha256:
+        print(text_sha256(a.lib))
+        return
     res = {k: v for k, v in kernel_resources(a.lib).items() if a.match in k}
     rows = [dict(name=k, **v) for k, v in sorted(res.items())]
     if a.out:
